@@ -235,6 +235,29 @@ def measured_traffic(kernel):
     return row["bytes_per_launch"], {"source": TRAFFIC_FILE, **{k: v for k, v in row.items() if k != "bytes_per_launch"}}
 
 
+DUMP_BYTES = 64_000_000
+
+
+def dump_outputs(out, path):
+    """--dump-outputs: every array of one frame's result dict as <path>/<name>.npy, float32 (float64 stays float64).  The
+    arrays share DUMP_BYTES, smallest first, each at most an equal share of what is left: one that fits is written whole in
+    its own shape, a larger one as a fixed sample of its flattened elements (seeded, sorted positions: the same for the
+    same arguments on every run and every build)."""
+    os.makedirs(path, exist_ok=True)
+    items = sorted(out.items(), key=lambda kv: (kv[1].numel(), kv[0]))
+    left = DUMP_BYTES // 4 - 1024 * len(items)              # float32 elements, minus room for the .npy headers
+    for n, (name, t) in enumerate(items):
+        t = t.detach() if t.dtype == torch.float64 else t.detach().float()
+        share = left // (len(items) - n) // (t.element_size() // 4)
+        if t.numel() > share:
+            pos = torch.randperm(t.numel(), generator=torch.Generator().manual_seed(0))[:share].sort().values
+            t = t.reshape(-1)[pos.to(t.device)]
+        arr = t.cpu().numpy()
+        np.save(os.path.join(path, name + ".npy"), arr)
+        left -= arr.size * (arr.itemsize // 4)
+        print(f"[bench] dump: {name} {tuple(out[name].shape)} -> {arr.shape}", file=sys.stderr, flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -249,14 +272,20 @@ def main():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-threads", type=int, default=0,
                     help="threads of the CPU oracle leg (default: every core the process can use -- affinity mask cut to the cgroup quota)")
-    ap.add_argument("--repeats", type=int, default=3,
-                    help="timed regions of --steps steps, back to back with the same barriers; `value` is the FIRST, all of them go to value_repeats")
+    ap.add_argument("--repeats", type=int, default=1,
+                    help="timed regions of --steps steps, back to back with the same barriers; `value` is the FIRST, all of them go to "
+                         "value_repeats (3: how far `value` moves from run to run)")
     ap.add_argument("--cpu-baseline-runs", type=int, default=3,
                     help="timed full-size runs of the CPU oracle (median reported); 3 = BASELINE.md's protocol, ~4 minutes")
-    ap.add_argument("--steps-720p", type=int, default=20,
+    ap.add_argument("--steps-720p", type=int, default=0,
                     help="extra timed steps at 1280x720 after the headline run (north_star asks for both sizes); 0 = skip")
     ap.add_argument("--no-profile", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last one returned (every array of rank 0's result dict) as "
+                         "DIR/<name>.npy, float32, at most 64 MB in all (see dump_outputs)")
     args = ap.parse_args()
+    if args.dump_outputs and args.steps < 1:
+        ap.error("--dump-outputs needs --steps >= 1")
     if args.gpus > 1 and "RANK" not in os.environ and "WORLD_SIZE" not in os.environ:
         spawn_ranks(args.gpus)                               # never returns
 
@@ -286,7 +315,7 @@ def main():
         f0, f2 = pairs[i % len(pairs)]
         k = i % len(runners)
         with torch.cuda.stream(streams[k]):
-            return runners[k](f0, f2, output_baseline=True)["final"]
+            return runners[k](f0, f2, output_baseline=True)
 
     def barrier():
         if world > 1:
@@ -312,7 +341,7 @@ def main():
                 f0s.copy_(pairs[0][0]); f2s.copy_(pairs[0][1])
                 streams[k].synchronize()
                 with torch.cuda.graph(g, stream=streams[k]):
-                    out = r(f0s, f2s, output_baseline=True)["final"]
+                    out = r(f0s, f2s, output_baseline=True)
             slots.append((g, f0s, f2s, out))
         eager_step = step
 
@@ -327,10 +356,16 @@ def main():
         for i in range(2):
             step(i)
         barrier()
+    last = [None]                                            # result dict of the last timed step
+
     def timed_region():
+        last[0] = None
         t0 = time.perf_counter()
         for i in range(args.steps):
-            step(i)
+            if i < args.steps - 1:
+                step(i)
+            else:
+                last[0] = step(i)                            # (earlier results are freed as they come, as always)
         barrier()
         return shard.reduce_counters(args.steps, time.perf_counter() - t0, device)
 
@@ -341,6 +376,8 @@ def main():
         repeats = [frames / elapsed] + [(lambda fe: fe[0] / fe[1])(timed_region()) for _ in range(max(0, args.repeats - 1))]
     except shard.ShardError:
         sys.exit(5)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(last[0], args.dump_outputs)             # (before anything else runs on the runners' buffers)
 
     # second size north_star names: the same fused frame at 1280x720, same barriers, same in-flight scheme (eager)
     value_720p = None

@@ -330,8 +330,48 @@ def gen_phasenet_only():
     save("phasenet_only_256", pair_seed=4, weight_seed=1, h=h, w=w, height=pyr.height, lab_pred=lab_pred.numpy())
 
 
+def gen_trained_like():
+    """PhaseNet and FusionNet with weights of the trained checkpoints' magnitude: seeded tensors rescaled to the committed
+    per-tensor statistics (tests/trained_stats.py), so realistic BatchNorm statistics / weight scales are pinned without
+    committing the checkpoints.  PhaseNet inputs come from oracle.synth.synthetic_vals(11, ...) and are NOT stored."""
+    _placeholders()
+    nets, synth = _oracle()
+    sys.path.insert(0, os.path.dirname(HERE))
+    import trained_stats
+    from oracle import layout_cpu
+    from src.fusion_net.fusion_net import FusionNet
+    from src.phase_net.phase_net import PhaseNet
+    from src.train import utils as rutils
+    from src.train.pyramid import DecompValues as RefVals
+    d = dict(phasenet_seed=7, fusionnet_seed=5, input_seed=11, h=48, w=64)
+    h, w = d["h"], d["w"]
+    height = layout_cpu.calc_pyr_height(h, w)
+    pyr = types.SimpleNamespace(height=height, nbands=4)
+    net = PhaseNet(pyr, torch.device("cpu"), num_img=2)
+    print(net.load_state_dict(trained_stats.state_dict_like_trained("phasenet", nets.phasenet_random_state_dict(0), seed=7)))
+    net.eval()
+    vin = rutils.get_concat_layers_inf(pyr, rutils.separate_vals(RefVals(*synth.synthetic_vals(11, 6, h, w, height)), 2))
+    with torch.no_grad():
+        out = net(net.normalize_vals(vin))
+    d["phasenet_low"] = out.low_level.numpy()
+    for k, (p, a) in enumerate(zip(out.phase, out.amplitude)):
+        d[f"phasenet_phase{k}"], d[f"phasenet_amp{k}"] = p.numpy(), a.numpy()
+    net = FusionNet()
+    print(net.load_state_dict(trained_stats.state_dict_like_trained("fusionnet", nets.fusionnet_random_state_dict(0), seed=5)))
+    net.eval()
+    g = torch.Generator().manual_seed(5)
+    r = lambda c: torch.rand((1, c, 40, 56), generator=g)
+    base, ada, ph, other, maps = r(3), r(3), r(3), r(6), r(3)
+    with torch.no_grad():
+        o0 = net(base, ada, ph, other, maps, variant=0)
+    d.update(base=base.numpy(), adacof=ada.numpy(), phase=ph.numpy(), other=other.numpy(), maps=maps.numpy(),
+             out_variant0=o0.numpy())
+    save("trained_like_nets", **d)
+
+
 GENERATORS = {"adacof": gen_adacof, "phasenet": gen_phasenet, "layout": gen_layout,
-              "fusionnet": gen_fusionnet, "adacofnet": gen_adacofnet, "phasenet_only": gen_phasenet_only}
+              "fusionnet": gen_fusionnet, "adacofnet": gen_adacofnet, "phasenet_only": gen_phasenet_only,
+              "trained_like": gen_trained_like}
 
 
 def main():

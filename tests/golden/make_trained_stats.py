@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Per-tensor statistics of the reference's TRAINED checkpoints (build container only: reads /root/reference; the
-checkpoints themselves are never committed).  -> tests/golden/trained_weight_stats.json
+checkpoints themselves are never committed).  -> tests/golden/trained_weight_stats.json and
+tests/golden/trained_checkpoint_layout.json (every entry's key and shape, integer counters included).
 
 The GPU parity tests draw seeded random tensors and rescale them tensor by tensor to these statistics
 (tests/trained_stats.py), so that the kernels also run on weights / folded BatchNorm scales of the magnitude a trained
@@ -22,20 +23,23 @@ def stats(t):
 
 
 def main():
-    out = {}
+    out, layout = {}, {}
     for name, rel in FILES.items():
         sd = torch.load(os.path.join(REF, rel), map_location="cpu")
         out[name] = {}
+        layout[name] = {k: list(v.shape) for k, v in sd.items() if torch.is_tensor(v)}
         for k, v in sd.items():
             if not torch.is_tensor(v) or not v.dtype.is_floating_point:
                 continue
             d = stats(v)
             d["shape"] = list(v.shape)
             out[name][k] = d
-    path = os.path.join(os.path.dirname(os.path.abspath(__file__)), "trained_weight_stats.json")
-    with open(path, "w") as f:
-        json.dump(out, f, indent=0, sort_keys=True)
-    print(path, {k: len(v) for k, v in out.items()})
+    here = os.path.dirname(os.path.abspath(__file__))
+    for fname, table in (("trained_weight_stats.json", out), ("trained_checkpoint_layout.json", layout)):
+        path = os.path.join(here, fname)
+        with open(path, "w") as f:
+            json.dump(table, f, indent=0, sort_keys=True)
+        print(path, {k: len(v) for k, v in table.items()})
 
 
 if __name__ == "__main__":

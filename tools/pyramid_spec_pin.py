@@ -17,7 +17,9 @@ middle frame is analytic, for
 
 Runs in the BUILD CONTAINER only (needs /root/reference/src/phase_net/phase_net.pt, loaded as data with
 map_location='cpu'; no reference code is imported).  Writes tests/golden/pyramid_spec_pin.json; the table is copied
-into DESIGN.md.  tests/test_oracle_pyramid_pin.py re-checks a reduced case whenever the checkpoint is present.
+into DESIGN.md.  It also writes tests/golden/pyramid_spec_fingerprint.npz, the oracle's decomposition of one seeded
+frame (`--fingerprint` writes only that, without the checkpoint): tests/test_oracle_pyramid_pin.py checks that the
+oracle still computes the spec the table was measured on.
 """
 import json
 import math
@@ -111,7 +113,31 @@ CASES = [("ours: ceil sizes, DC at h//2", {}, "plain"),
 SHIFTS = [(1.0, 0.5), (2.0, -1.5), (3.5, -2.25), (5.0, 3.0)]
 
 
+FINGERPRINT = os.path.join(ROOT, "tests", "golden", "pyramid_spec_fingerprint.npz")
+
+
+def spec_fingerprint(size=256, seed=1, shift=(3.5, -2.25), step=4):
+    """The oracle's decomposition of one seeded frame (L channel) on a stride-`step` grid: residuals as they are, bands as
+    complex coefficients (amplitude * exp(i phase), no wrap at +-pi), each with its full shape.  Written next to the table
+    so that a test without the checkpoint can tell whether the oracle still computes the spec the table was measured on."""
+    f0, _, _ = synth.translating_pair(seed, size, size, shift=shift)
+    lab = color_cpu.rgb2lab_single(torch.from_numpy(f0))[:1].float()
+    vals = pyramid_cpu.Pyramid(layout_cpu.calc_pyr_height(size, size), 4, np.sqrt(2)).filter(lab)
+    parts = {"high": vals.high_level, "low": vals.low_level}
+    parts.update({f"band{k}": torch.view_as_real(torch.polar(a, p)) for k, (p, a) in enumerate(zip(vals.phase, vals.amplitude))})
+    out = {}
+    for name, t in parts.items():
+        out[name + "_shape"] = np.array(t.shape)
+        out[name] = (t[:, :, ::step, ::step] if name.startswith("band") else t[..., ::step, ::step]).numpy()
+    return out
+
+
+def write_fingerprint(out=FINGERPRINT):
+    np.savez_compressed(out, **spec_fingerprint())
+
+
 def main(size=256, seeds=(0, 1, 2), out=os.path.join(ROOT, "tests", "golden", "pyramid_spec_pin.json")):
+    write_fingerprint()
     sd = torch.load(CKPT, map_location="cpu")
     torch.set_num_threads(8)
     rows = []
@@ -135,4 +161,7 @@ def main(size=256, seeds=(0, 1, 2), out=os.path.join(ROOT, "tests", "golden", "p
 
 
 if __name__ == "__main__":
-    main()
+    if sys.argv[1:] == ["--fingerprint"]:
+        write_fingerprint()
+    else:
+        main()
