@@ -20,6 +20,18 @@
 //   * (rgbx entry point) frames are pixel-interleaved (16-B gathers) and the workgroup's frame neighbourhood
 //     (tile + tap reach + a 4-pixel offset margin) is staged in LDS, so almost every bilinear corner is an LDS read;
 //     measured at 1088x1920 (offsets ~N(0,2) clipped to +-8): planar gathers 1.29 ms -> rgbx 0.94 ms -> LDS window 0.56 ms.
+//
+//   vfi_adacof_backward : FunctionAdaCoF.backward (reference adacof.py:364-445, kernel texts :67-258), all three
+//                         gradients (weight, offset_i, offset_j) in ONE launch instead of three
+//
+// Roofline: HBM.  For F=5, C=3 it reads the 3 F*F planes (w, alpha, beta: 300 B/px), writes the 3 gradient planes
+// (300 B/px) and reads the C deltas (12 B/px): ~612 B/px, 1.27 GB at a 1080x1920 output (~0.3 ms at 4.3 TB/s); the
+// frame gathers are served by L1/L2.  Design: one thread per output pixel loads its C deltas once into registers
+// and walks the F*F taps; per tap it reads (w, alpha, beta), gathers the four clamped corners of every channel ONCE
+// for all three gradients (the reference re-reads taps and deltas in each of its three kernels, per channel) and
+// writes one element of each gradient plane.  No atomics, no cross-thread reduction: deterministic.  Measured at
+// 1080x1920, F=5: 0.75 ms (1.7 TB/s effective) -- like the planar forward it is bound by the per-corner 4-B gathers
+// (L1 address / tag throughput), not by HBM: FETCH_SIZE + WRITE_SIZE come to ~1 GB per launch, ~1 TB/s.
 #include "vfi_common.h"
 
 #include <cstdlib>
@@ -410,6 +422,92 @@ __global__ __launch_bounds__(256, MIN_WAVES) void adacof_fused_kernel(
     }
 }
 
+// ---- backward: the three gradients of FunctionAdaCoF.backward in one pass ----------------------
+// One tap of adacof.py:118-123 (weight), :183-188 (alpha) and :248-253 (beta), summed over the C channels.  The corners,
+// clamps and fractions are those of tap_accumulate; A and B carry no gradient, so d/dalpha only sees the fractions.
+// CT > 0: the C deltas of this pixel are in registers (`dreg`); CT == 0: runtime C, deltas read from `dglob` (cached).
+// Returns sum_c delta*bilinear in gw and the UN-weighted offset sums in sa / sb (the caller multiplies by w).
+template <int CT>
+__device__ __forceinline__ void tap_gradient(const float *__restrict__ in, size_t in_plane, int C, int Hin, int Win,
+                                             int row, int col, float alpha, float beta, const float *dreg,
+                                             const float *__restrict__ dglob, size_t plane, float &gw, float &sa,
+                                             float &sb) {
+    const int A = (int)alpha;
+    const int B = (int)beta;
+    const float fa = alpha - (float)A;
+    const float fb = beta - (float)B;
+    const int i0 = min(max(row + A, 0), Hin - 1);
+    const int i1 = min(max(row + A + 1, 0), Hin - 1);
+    const int j0 = min(max(col + B, 0), Win - 1);
+    const int j1 = min(max(col + B + 1, 0), Win - 1);
+    const float ga = 1.0f - fa, gb = 1.0f - fb;
+    const float w00 = ga * gb, w10 = fa * gb, w01 = ga * fb, w11 = fa * fb;
+    const int o00 = i0 * Win + j0, o10 = i1 * Win + j0, o01 = i0 * Win + j1, o11 = i1 * Win + j1;
+    gw = 0.0f; sa = 0.0f; sb = 0.0f;
+    const int nc = CT > 0 ? CT : C;
+#pragma unroll
+    for (int c = 0; c < nc; ++c) {
+        const float *p = in + (size_t)c * in_plane;
+        const float delta = CT > 0 ? dreg[c] : dglob[(size_t)c * plane];
+        const float v00 = p[o00], v10 = p[o10], v01 = p[o01], v11 = p[o11];
+        gw += delta * (v00 * w00 + v10 * w10 + v01 * w01 + v11 * w11);
+        sa += delta * ((v10 - v00) * gb + (v11 - v01) * fb);
+        sb += delta * ((v01 - v00) * ga + (v11 - v10) * fa);
+    }
+}
+
+// Deterministic by construction: every (tap, pixel) gradient element is written by exactly one thread, once.
+template <int CT, int VEC>
+__global__ __launch_bounds__(256) void adacof_backward_kernel(
+    const float *__restrict__ grad_output, const float *__restrict__ input, const float *__restrict__ weight,
+    const float *__restrict__ offset_i, const float *__restrict__ offset_j, float *__restrict__ grad_weight,
+    float *__restrict__ grad_offset_i, float *__restrict__ grad_offset_j, int Crt, int Hin, int Win, int H, int W,
+    int F, int dil) {
+    constexpr int CR = CT > 0 ? CT : 1;
+    const int C = CT > 0 ? CT : Crt;
+    const int x0 = (blockIdx.x * 64 + threadIdx.x) * VEC;
+    const int y = blockIdx.y * 4 + threadIdx.y;
+    const int n = blockIdx.z;
+    if (x0 >= W || y >= H) return;
+    const size_t plane = (size_t)H * W;
+    const size_t in_plane = (size_t)Hin * Win;
+    const float *in = input + (size_t)n * C * in_plane;
+    const size_t pix = (size_t)y * W + x0;
+    const size_t tbase = (size_t)n * F * F * plane + pix;
+    const float *go = grad_output + (size_t)n * C * plane + pix;
+    const bool want_off = grad_offset_i != nullptr || grad_offset_j != nullptr;
+
+    float d[VEC][CR] = {};   // gradLoss[n, :, y, x0 .. x0+VEC-1], loaded once
+    if constexpr (CT > 0) {
+#pragma unroll
+        for (int c = 0; c < CT; ++c) {
+            Vec<VEC> t;
+            t.load(go + (size_t)c * plane);
+#pragma unroll
+            for (int v = 0; v < VEC; ++v) d[v][c] = t.v[v];
+        }
+    }
+
+    for (int k = 0; k < F; ++k)
+        for (int l = 0; l < F; ++l) {
+            const size_t t = tbase + (size_t)(k * F + l) * plane;
+            Vec<VEC> w, a, b;
+            a.load(offset_i + t);
+            b.load(offset_j + t);
+            if (want_off) w.load(weight + t);
+            float gw[VEC], ga[VEC], gb[VEC];
+#pragma unroll
+            for (int v = 0; v < VEC; ++v) {
+                tap_gradient<CT>(in, in_plane, C, Hin, Win, y + k * dil, x0 + v + l * dil, a.v[v], b.v[v], d[v],
+                                 go + v, plane, gw[v], ga[v], gb[v]);
+                if (want_off) { ga[v] *= w.v[v]; gb[v] *= w.v[v]; }
+            }
+            if (grad_weight) store_vec<VEC>(grad_weight + t, gw);
+            if (grad_offset_i) store_vec<VEC>(grad_offset_i + t, ga);
+            if (grad_offset_j) store_vec<VEC>(grad_offset_j + t, gb);
+        }
+}
+
 inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
 }  // namespace
@@ -441,6 +539,41 @@ extern "C" int vfi_adacof_forward(const float *input, const float *weight, const
     else         { if (vec) LAUNCH(1, 4); else LAUNCH(1, 1); }
 #undef LAUNCH
     return vfi::check_launch("vfi_adacof_forward");
+}
+
+extern "C" int vfi_adacof_backward(const float *grad_output, const float *input, const float *weight,
+                                   const float *offset_i, const float *offset_j, float *grad_weight,
+                                   float *grad_offset_i, float *grad_offset_j, int N, int C, int Hin, int Win,
+                                   int H, int W, int F, int dilation, vfi_stream_t stream) {
+    const bool want_off = grad_offset_i || grad_offset_j;
+    VFI_REQUIRE(grad_weight || want_off, VFI_ERR_INVALID_ARG, "vfi_adacof_backward: no gradient requested");
+    VFI_REQUIRE(grad_output && input && offset_i && offset_j && (weight || !want_off), VFI_ERR_INVALID_ARG,
+                "vfi_adacof_backward: null pointer");
+    VFI_REQUIRE(N > 0 && C > 0 && H > 0 && W > 0 && F > 0 && dilation > 0, VFI_ERR_INVALID_ARG,
+                "vfi_adacof_backward: non-positive size");
+    // adacof.py:326-327 (asserted again in the reference's backward, :376-377)
+    VFI_REQUIRE(Hin - ((F - 1) * dilation + 1) == H - 1 && Win - ((F - 1) * dilation + 1) == W - 1,
+                VFI_ERR_SHAPE, "vfi_adacof_backward: input %dx%d does not match output %dx%d for F=%d dilation=%d",
+                Hin, Win, H, W, F, dilation);
+    VFI_REQUIRE((long long)Hin * Win < (1ll << 31) && (long long)N * F * F * H * W < (1ll << 40) &&
+                    (long long)N * C * Hin * Win < (1ll << 40),
+                VFI_ERR_UNSUPPORTED, "vfi_adacof_backward: tensor too large");
+    if (!want_off) weight = nullptr;   // not read
+    // One pixel per thread: measured on MI355X at 1080x1920, C = 3, F = 5 (tools/adacof_backward_rate.py), VEC = 1
+    // takes 0.75 ms, VEC = 4 0.98 ms (0.97 ms with the F = 5 loops unrolled).  The per-corner gathers, not HBM, bound
+    // the kernel, and 64 lanes on 64 adjacent pixels touch fewer cache lines per gather instruction.
+    hipStream_t s = vfi::as_stream(stream);
+    dim3 block(64, 4);
+    dim3 grid(vfi::ceil_div(W, 64), vfi::ceil_div(H, 4), N);
+    VFI_REQUIRE(grid.z <= 65535 && grid.y <= 65535, VFI_ERR_UNSUPPORTED, "vfi_adacof_backward: grid too large");
+#define LAUNCH(CT)                                                                                           \
+    hipLaunchKernelGGL((adacof_backward_kernel<CT, 1>), grid, block, 0, s, grad_output, input, weight, offset_i, \
+                       offset_j, grad_weight, grad_offset_i, grad_offset_j, C, Hin, Win, H, W, F, dilation)
+    if (C == 3) LAUNCH(3);
+    else if (C == 1) LAUNCH(1);
+    else LAUNCH(0);
+#undef LAUNCH
+    return vfi::check_launch("vfi_adacof_backward");
 }
 
 static int adacof_fused_impl(const float *frame0, const float *frame2, const float *w1,

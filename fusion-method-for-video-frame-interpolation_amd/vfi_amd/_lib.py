@@ -22,6 +22,7 @@ class VfiLibraryError(RuntimeError):
 SIGNATURES = {
     "vfi_debug_poison_lds": [c_s],
     "vfi_adacof_forward": [c_f] * 5 + [c_i] * 8 + [c_s],
+    "vfi_adacof_backward": [c_f] * 8 + [c_i] * 8 + [c_s],
     "vfi_adacof_fused": [c_f] * 13 + [c_i] * 6 + [c_s],
     "vfi_conv2d_packed_floats": [c_i] * 3,
     "vfi_conv2d_algo": [c_i] * 9,

@@ -3,8 +3,10 @@
 ``FunctionAdaCoF.apply(input, weight, offset_i, offset_j, dilation)`` keeps the reference
 signature (adacof.py:313-315) and its asserts (adacof.py:326-332); the work is one launch of
 ``vfi_adacof_forward`` (csrc/vfi_adacof.hip) on torch's current HIP stream instead of a
-per-shape NVRTC compile.  Inference only: the reference's three backward kernels
-(adacof.py:67-258) are training code and out of scope, so ``backward`` raises.
+per-shape NVRTC compile.  ``backward`` replaces the reference's three gradient kernels
+(adacof.py:67-258, launched from :364-445) with one launch of ``vfi_adacof_backward`` that writes the
+weight and both offset gradients, so the op can be trained through.  The other entry points of this
+module (``adacof_fused``) are inference only.
 """
 import math
 
@@ -28,6 +30,7 @@ class FunctionAdaCoF(torch.autograd.Function):
         assert offset_j.is_contiguous()
         if not input.is_cuda:
             raise NotImplementedError()                   # adacof.py:356-357
+        ctx.save_for_backward(input, weight, offset_i, offset_j)   # adacof.py:315
         output = torch.empty((n, c, h, w), dtype=input.dtype, device=input.device)
         _lib.call("vfi_adacof_forward", _lib.dptr(input, "input"), _lib.dptr(weight, "weight"),
                   _lib.dptr(offset_i, "offset_i"), _lib.dptr(offset_j, "offset_j"),
@@ -36,7 +39,36 @@ class FunctionAdaCoF(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, grad_output):
-        raise NotImplementedError("vfi_amd implements the inference path only")
+        """Gradients of (input, weight, offset_i, offset_j, dilation), as the reference returns them (adacof.py:364-445).
+
+        The input gradient is NOT computed: when ``input`` requires grad it is a zero tensor, exactly what the
+        reference returns (adacof.py:382 allocates it and no kernel fills it); otherwise None.  The weight and
+        offset gradients are produced only where ``ctx.needs_input_grad`` asks for them (the reference gates
+        both offset gradients on offset_i).  A non-contiguous ``grad_output`` (e.g. from ``out.sum()``) is made
+        contiguous instead of asserted on (adacof.py:380)."""
+        input, weight, offset_i, offset_j = ctx.saved_tensors
+        dilation = ctx.dilation
+        n, c, hin, win = input.shape
+        f = int(math.sqrt(weight.size(1)))
+        h, w = weight.size(2), weight.size(3)
+        grad_output = grad_output.contiguous()
+        need = ctx.needs_input_grad
+        new = lambda: torch.empty((n, f * f, h, w), dtype=input.dtype, device=input.device)
+        grad_input = torch.zeros_like(input) if need[0] else None
+        grad_weight = new() if need[1] else None
+        grad_offset_i = new() if need[2] else None
+        grad_offset_j = new() if need[3] else None
+        n_out = sum(g is not None for g in (grad_weight, grad_offset_i, grad_offset_j))
+        if n_out:
+            want_off = grad_offset_i is not None or grad_offset_j is not None
+            d = _lib.dptr
+            _lib.call("vfi_adacof_backward", d(grad_output, "grad_output"), d(input, "input"),
+                      d(weight, "weight") if want_off else None, d(offset_i, "offset_i"), d(offset_j, "offset_j"),
+                      d(grad_weight), d(grad_offset_i), d(grad_offset_j), n, c, hin, win, h, w, f, int(dilation),
+                      _lib.stream_ptr(),
+                      work=("byte", float(n) * h * w * (4 * c + 4 * f * f * (2 + want_off + n_out)),
+                            "adacof_backward_kernel"))
+        return grad_input, grad_weight, grad_offset_i, grad_offset_j, None
 
 
 def adacof_fused(frame0, frame2, w1, a1, b1, w2, a2, b2, occ, dilation,

@@ -74,6 +74,21 @@ int vfi_adacof_forward(const float *input, const float *weight, const float *off
                        const float *offset_j, float *output, int N, int C, int Hin, int Win,
                        int H, int W, int F, int dilation, vfi_stream_t stream);
 
+/* Replaces FunctionAdaCoF.backward + kernel_AdaCoF_updateGradWeight / ...updateGradAlpha / ...updateGradBeta
+ * (src/adacof/cupy_module/adacof.py:364-445 and :67-258) with ONE launch that produces all three gradients.
+ *   grad_output (N, C, H, W);  input, weight, offset_i, offset_j as in vfi_adacof_forward
+ *   grad_weight, grad_offset_i, grad_offset_j  (N, F*F, H, W), each may be NULL (not produced; at least one
+ *   is required).  weight may be NULL when both offset gradients are NULL.
+ * Semantics are the reference's (same truncation, per-corner clamps and fractions as the forward; A = (int)alpha
+ * carries no gradient), except that the channel sum runs over all C channels (the reference stops at c < 3).
+ * Deterministic: every output element is written by exactly one thread.  No input gradient (the reference's is
+ * an unfilled zero tensor). */
+int vfi_adacof_backward(const float *grad_output, const float *input, const float *weight,
+                        const float *offset_i, const float *offset_j,
+                        float *grad_weight, float *grad_offset_i, float *grad_offset_j,
+                        int N, int C, int Hin, int Win, int H, int W, int F, int dilation,
+                        vfi_stream_t stream);
+
 /* One fused pass over both sampling sides of AdaCoFNet.forward
  * (src/fusion_net/fusion_adacofnet.py:195-213; plain variant src/adacof/models/adacofnet.py:195-199):
  *   t1 = AdaCoF(ReplicationPad(frame0), W1, A1, B1);  t2 = AdaCoF(ReplicationPad(frame2), W2, A2, B2)
