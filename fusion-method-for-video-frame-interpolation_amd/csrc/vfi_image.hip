@@ -8,6 +8,9 @@
 // costs the reference 66 s per 1080p frame on 8 CPU cores.
 #include "vfi_common.h"
 
+#include <cstdlib>
+#include <cstring>
+
 namespace {
 
 using vfi::ceil_div;
@@ -327,6 +330,207 @@ __global__ __launch_bounds__(256) void median_rank_kernel(const float *__restric
     }
 }
 
+// ---- exact median, radix rank + snake-walking bitsets (the default fast path) -----------------------------------------
+// A 64 x 64 output tile and its (64+S-1)^2 input window (<= 16384 positions for every S <= 64), 16 waves:
+//   1. ranks: the window's positions are sorted by key with a stable LSD radix sort in LDS, one bit per pass (a 1-bit split:
+//      ballot + mbcnt inside a wave, one 16-entry scan across the waves), skipping the bits that no key of the window
+//      changes.  Stability makes every rank unique by position, so no position travels with the key; positions are 16 bit;
+//   2. every wave walks a 4-row strip of the tile as a snake (right along row 0, one step down, left along row 1, ...) with
+//      one bitset of the ranks in its SxS window: the S*S-insert fill is paid once per wave, every step then clears S bits
+//      and sets S bits (one LDS atomic of each kind per wave, a lane per row or column of the window) and moves a
+//      (word, popcount-below) cursor, kept wave-uniform, to the median rank;
+//   3. the median is the sorted key at that rank: an element of the window, bit-exact with scipy.
+// LDS: keys 4 B + two position lists 2 B each per slot, 8 B x 1024 x ceil(U / 1024) (106.5 KiB at S = 50): the bitsets
+// (16 x U/32 words) alias the position list that is dead once the ranks are built.
+constexpr int kWkT = 64, kWkThreads = 1024, kWkWaves = kWkThreads / 64, kWkRows = kWkT / kWkWaves, kWkMaxE = 16;
+__host__ __device__ constexpr int med_walk_elems(int S) { return ((kWkT + S - 1) * (kWkT + S - 1) + kWkThreads - 1) / kWkThreads; }
+__host__ __device__ constexpr size_t med_walk_lds(int S) { return (size_t)8 * kWkThreads * med_walk_elems(S); }
+static_assert(med_walk_elems(64) <= kWkMaxE, "the 64x64 tile must hold the window of every size the ABI accepts");
+
+#ifdef MEDIAN_STAMPS
+// diagnostic build (tools/probes/median_stamps.py): shader cycles of every wave of median_walk_kernel summed per phase
+// (load, key mask, radix passes, rank build, bitset fill + first cursor, slide + cursor walk), then the wave count and
+// the number of radix passes -- never part of the shipped library
+__device__ unsigned long long med_stamps[8];
+#define MED_STAMP(k) stamp[k] = __builtin_amdgcn_s_memtime()
+#else
+#define MED_STAMP(k)
+#endif
+
+__device__ __forceinline__ unsigned lanes_below(unsigned long long m) {    // set bits of m below this lane
+    return __builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
+}
+
+__global__ __launch_bounds__(kWkThreads) void median_walk_kernel(const float *__restrict__ x, float *__restrict__ y, int H, int W, int S) {
+    extern __shared__ unsigned smem[];
+    __shared__ unsigned wsum[kWkWaves], vary;
+#ifdef MEDIAN_STAMPS
+    unsigned long long stamp[7];
+#endif
+    MED_STAMP(0);
+    const int PW = kWkT + S - 1, U = PW * PW, E = med_walk_elems(S), N = E * kWkThreads;
+    unsigned *K = smem;                                                    // [N] key of each position; later: key of each rank
+    unsigned short *src = reinterpret_cast<unsigned short *>(smem + N);     // [N] position list (ping)
+    unsigned short *dst = src + N;                                          // [N] position list (pong)
+    const int n = blockIdx.z, x0 = blockIdx.x * kWkT, y0 = blockIdx.y * kWkT, lo_off = S / 2;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const float *p = x + (size_t)n * H * W;
+    if (tid == 0) vary = 0u;
+    for (int pos = tid; pos < N; pos += kWkThreads) {       // window row-major; padding sorts last (stable: after real 0xffffffff)
+        unsigned k = 0xffffffffu;
+        if (pos < U) {
+            const int r = pos / PW, c = pos - r * PW;
+            k = key_of(p[(size_t)sym_reflect(y0 - lo_off + r, H) * W + sym_reflect(x0 - lo_off + c, W)]);
+        }
+        K[pos] = k;
+        src[pos] = (unsigned short)pos;
+    }
+    __syncthreads();
+    MED_STAMP(1);
+    {   // the bits in which some key of the window differs from the first: a pass over any other bit keeps the order
+        const unsigned k0 = K[0];
+        unsigned v = 0u;
+        for (int pos = tid; pos < U; pos += kWkThreads) v |= K[pos] ^ k0;
+        for (int o = 32; o > 0; o >>= 1) v |= __shfl_xor(v, o, 64);
+        if (lane == 0 && v) atomicOr(&vary, v);
+    }
+    __syncthreads();
+    MED_STAMP(2);
+    const unsigned varying = vary;
+    // Sequence index of slot j of a lane: wave * 64 E + 64 j + lane (each wave owns a contiguous span).
+    const int wbase = wave * 64 * E;
+    for (int b = 0; b < 32; ++b) {
+        if (!((varying >> b) & 1u)) continue;
+        unsigned short pj[kWkMaxE];
+        unsigned ones = 0u, zc = 0u;
+#pragma unroll
+        for (int j = 0; j < kWkMaxE; ++j)
+            if (j < E) {
+                pj[j] = src[wbase + 64 * j + lane];
+                const unsigned bit = (K[pj[j]] >> b) & 1u;
+                ones |= bit << j;
+                zc += (unsigned)__popcll(__ballot(bit == 0u));
+            }
+        if (lane == 0) wsum[wave] = zc;
+        __syncthreads();
+        unsigned zbase = 0u, ztot = 0u;
+#pragma unroll
+        for (int w = 0; w < kWkWaves; ++w) {
+            const unsigned s = wsum[w];
+            ztot += s;
+            zbase += w < wave ? s : 0u;
+        }
+        unsigned zi = zbase, oi = ztot + (unsigned)wbase - zbase;   // next slot of this wave's zeros / ones
+#pragma unroll
+        for (int j = 0; j < kWkMaxE; ++j)
+            if (j < E) {
+                const bool one = (ones >> j) & 1u;
+                const unsigned long long zm = __ballot(!one);
+                const unsigned zb = lanes_below(zm), nz = (unsigned)__popcll(zm);
+                dst[one ? oi + (unsigned)lane - zb : zi + zb] = pj[j];
+                zi += nz;
+                oi += 64u - nz;
+            }
+        __syncthreads();
+        unsigned short *t = src; src = dst; dst = t;
+    }
+    MED_STAMP(3);
+    // src: positions in rank order.  dst becomes R (rank of each position), K the key of each rank.
+    unsigned kv[kWkMaxE];
+#pragma unroll
+    for (int j = 0; j < kWkMaxE; ++j)
+        if (j < E) {
+            const int i = tid + j * kWkThreads;
+            const unsigned pos = src[i];
+            kv[j] = K[pos];
+            dst[pos] = (unsigned short)i;
+        }
+    __syncthreads();
+#pragma unroll
+    for (int j = 0; j < kWkMaxE; ++j)
+        if (j < E) K[tid + j * kWkThreads] = kv[j];
+    const unsigned short *R = dst;
+    const int nwords = N / 32;
+    unsigned *bits = reinterpret_cast<unsigned *>(src) + wave * nwords;     // this wave's bitset, in the dead position list
+    __syncthreads();
+    MED_STAMP(4);
+    const int r0 = wave * kWkRows;
+    const int cv = min(kWkT, W - x0), rv = min(kWkRows, H - y0 - r0);    // valid columns of the tile / rows of the strip
+    if (rv > 0) {   // (no barrier below)
+        for (int w = lane; w < nwords; w += 64) bits[w] = 0u;
+        for (int i = lane; i < S * S; i += 64) {            // window of output (r0, 0)
+            const int r = i / S, c = i - r * S;
+            const unsigned rk = R[(r0 + r) * PW + c];
+            atomicOr(&bits[rk >> 5], 1u << (rk & 31));
+        }
+        const int need = (S * S) / 2 + 1;                   // the median is the need-th smallest rank in the window
+        int ptr = 0, below = 0;                             // below = set bits in words [0, ptr)
+        for (int w0 = 0;; w0 += 64) {                        // first cursor: 64 words per probe, prefix sum across the wave
+            const int cnt = w0 + lane < nwords ? __popc(bits[w0 + lane]) : 0;
+            int inc = cnt;
+#pragma unroll
+            for (int o = 1; o < 64; o <<= 1) {
+                const int t = __shfl_up(inc, o, 64);
+                if (lane >= o) inc += t;
+            }
+            const unsigned long long hit = __ballot(below + inc >= need);
+            if (hit) {
+                const int L = __ffsll((long long)hit) - 1;
+                ptr = w0 + L;
+                below += __shfl(inc - cnt, L, 64);
+                break;
+            }
+            below += __shfl(inc, 63, 64);
+        }
+        MED_STAMP(5);
+        const bool act = lane < S;
+        for (int j = 0; j < rv; ++j) {
+            const int r = r0 + j;
+            const bool right = (j & 1) == 0;
+            float res = 0.0f;
+            for (int s = 0; s < cv; ++s) {
+                const int col = right ? s : cv - 1 - s;
+                if (s > 0 || j > 0) {
+                    int po, pi;                               // position leaving / entering the window on this lane
+                    if (s == 0) { po = (r - 1) * PW + col + lane; pi = (r + S - 1) * PW + col + lane; }        // one row down
+                    else if (right) { po = (r + lane) * PW + col - 1; pi = (r + lane) * PW + col + S - 1; }     // one column right
+                    else { po = (r + lane) * PW + col + S; pi = (r + lane) * PW + col; }                        // one column left
+                    unsigned ro = 0u, ri = 0u;
+                    if (act) {
+                        ro = R[po];
+                        ri = R[pi];
+                        atomicAnd(&bits[ro >> 5], ~(1u << (ro & 31)));
+                        atomicOr(&bits[ri >> 5], 1u << (ri & 31));
+                    }
+                    below += __popcll(__ballot(act && (int)(ri >> 5) < ptr)) - __popcll(__ballot(act && (int)(ro >> 5) < ptr));
+                }
+                // the LDS serves a wave's operations in order: these reads see the atomics above
+                while (below >= need) { --ptr; below -= __popc(bits[ptr]); }
+                unsigned wv = bits[ptr];
+                while (below + __popc(wv) < need) { below += __popc(wv); wv = bits[++ptr]; }
+                int k = need - below, bit = 0;                // k-th set bit of wv (1-based), by halving
+#pragma unroll
+                for (int wd = 16; wd > 0; wd >>= 1) {
+                    const int c = __popc(wv & ((1u << wd) - 1u));
+                    if (k > c) { k -= c; wv >>= wd; bit += wd; }
+                }
+                const float v = float_of(K[ptr * 32 + bit]);
+                res = lane == col ? v : res;
+            }
+            if (lane < cv) y[(size_t)n * H * W + (size_t)(y0 + r) * W + x0 + lane] = res;
+        }
+    }
+    MED_STAMP(6);
+#ifdef MEDIAN_STAMPS
+    if (lane == 0) {
+        const int last = rv > 0 ? 6 : 4;
+        for (int k = 1; k <= last; ++k) atomicAdd(&med_stamps[k - 1], stamp[k] - stamp[k - 1]);
+        atomicAdd(&med_stamps[6], 1ull);
+        if (tid == 0) atomicAdd(&med_stamps[7], (unsigned long long)__popc(varying));
+    }
+#endif
+}
+
 // ---- quality scoring (reference src/evaluation/evaluate_image.py:7-30) ---------------------------------------------
 // Deterministic two-stage reductions: per-block partial sums in double, then one block adds them in fixed order.
 constexpr int kRedBlocks = 1024;
@@ -491,23 +695,57 @@ extern "C" int vfi_gaussian_filter(const float *x, float *tmp, float *y, int N, 
     return vfi::check_launch("vfi_gaussian_filter");
 }
 
+#ifdef MEDIAN_STAMPS
+extern "C" int vfi_debug_median_stamps(unsigned long long *host, int reset) {
+    if (reset) {
+        const unsigned long long z[8] = {};
+        return hipMemcpyToSymbol(HIP_SYMBOL(med_stamps), z, sizeof(z)) == hipSuccess ? 0 : -1;
+    }
+    return hipMemcpyFromSymbol(host, HIP_SYMBOL(med_stamps), sizeof(unsigned long long) * 8) == hipSuccess ? 0 : -1;
+}
+#endif
+
+namespace {
+// VFI_MEDIAN_PATH (read at every call, so that a test can compare the kernels inside one process): "walk" (default) =
+// median_walk_kernel, "rank" = the 16x64 bitonic-rank kernel, "bisect" = the bisection kernel; size 1 always bisects
+enum class MedianPath { walk, rank, bisect };
+MedianPath median_path() {
+    const char *e = getenv("VFI_MEDIAN_PATH");
+    if (e && !strcmp(e, "rank")) return MedianPath::rank;
+    if (e && !strcmp(e, "bisect")) return MedianPath::bisect;
+    return MedianPath::walk;
+}
+
+int set_max_lds(const void *kernel, bool *done_dev, int bytes) {    // once per device: idempotent
+    bool &done = done_dev[vfi::current_device()];
+    if (done) return VFI_OK;
+    hipError_t e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+    if (e != hipSuccess) return vfi::fail(VFI_ERR_LAUNCH, "vfi_median_filter: set LDS size: %s", hipGetErrorString(e));
+    done = true;
+    return VFI_OK;
+}
+}  // namespace
+
 extern "C" int vfi_median_filter(const float *x, float *y, int N, int H, int W, int size, vfi_stream_t stream) {
     VFI_REQUIRE(x && y, VFI_ERR_INVALID_ARG, "vfi_median_filter: null pointer");
     VFI_REQUIRE(N > 0 && H > 0 && W > 0 && size >= 1, VFI_ERR_INVALID_ARG, "vfi_median_filter: bad arguments");
     VFI_REQUIRE(size <= 64, VFI_ERR_UNSUPPORTED, "vfi_median_filter: size %d > 64", size);
     VFI_REQUIRE(N <= 65535, VFI_ERR_UNSUPPORTED, "vfi_median_filter: batch");
-    if ((kRkTW + size - 1) * (kRkTH + size - 1) <= kRkN && size >= 2) {
-        constexpr size_t lds = kRkLds;   // 113 KiB
-        static bool attr_done_dev[vfi::kMaxDevices] = {};  // per device, idempotent
-        bool &attr_done = attr_done_dev[vfi::current_device()];
-        if (!attr_done) {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(median_rank_kernel),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            if (e != hipSuccess) return vfi::fail(VFI_ERR_LAUNCH, "vfi_median_filter: set LDS size: %s", hipGetErrorString(e));
-            attr_done = true;
-        }
+    const MedianPath path = size >= 2 ? median_path() : MedianPath::bisect;
+    if (path == MedianPath::walk) {
+        static bool attr_done_dev[vfi::kMaxDevices] = {};
+        const int rc = set_max_lds(reinterpret_cast<const void *>(median_walk_kernel), attr_done_dev, (int)med_walk_lds(64));
+        if (rc != VFI_OK) return rc;
+        dim3 grid(ceil_div(W, kWkT), ceil_div(H, kWkT), N);
+        hipLaunchKernelGGL(median_walk_kernel, grid, dim3(kWkThreads), med_walk_lds(size), vfi::as_stream(stream), x, y, H, W, size);
+        return vfi::check_launch("vfi_median_filter");
+    }
+    if (path == MedianPath::rank && (kRkTW + size - 1) * (kRkTH + size - 1) <= kRkN) {
+        static bool attr_done_dev[vfi::kMaxDevices] = {};
+        const int rc = set_max_lds(reinterpret_cast<const void *>(median_rank_kernel), attr_done_dev, (int)kRkLds);   // 113 KiB
+        if (rc != VFI_OK) return rc;
         dim3 grid(ceil_div(W, kRkTW), ceil_div(H, kRkTH), N);
-        hipLaunchKernelGGL(median_rank_kernel, grid, dim3(256), lds, vfi::as_stream(stream), x, y, H, W, size);
+        hipLaunchKernelGGL(median_rank_kernel, grid, dim3(256), kRkLds, vfi::as_stream(stream), x, y, H, W, size);
         return vfi::check_launch("vfi_median_filter");
     }
     const size_t lds = (size_t)(kMedTW + size - 1) * (kMedTH + size - 1) * sizeof(unsigned);

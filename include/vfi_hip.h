@@ -17,7 +17,7 @@
  *     Workspace is caller-provided or owned by an explicit plan object.
  *   - Process-wide state is limited to idempotent per-device launch setup (the dynamic-LDS
  *     attribute of three kernels, the CU count), tuning switches read once from the
- *     environment (VFI_CONV_WINOGRAD, VFI_CONV_WINOGRAD4, VFI_CONV_STREAM1X1, VFI_ADACOF_VARIANT, VFI_ADACOF_MARGIN; VFI_CONV_WINOGRAD4M at every call) and the
+ *     environment (VFI_CONV_WINOGRAD, VFI_CONV_WINOGRAD4, VFI_CONV_STREAM1X1, VFI_ADACOF_VARIANT, VFI_ADACOF_MARGIN; VFI_CONV_WINOGRAD4M and VFI_MEDIAN_PATH at every call) and the
  *     thread-local last-error string; everything else lives in explicit plan objects,
  *     whose tables are immutable after creation and whose workspace belongs to ONE stream
  *     at a time (frames in flight on different streams use different plans).
@@ -384,7 +384,8 @@ int vfi_gaussian_filter(const float *x, float *tmp, float *y, int N, int H, int 
 
 /* scipy.ndimage.median_filter(x, size=size) per (H,W) image: size x size window covering
  * [i - size/2, i - size/2 + size - 1], mode='reflect', rank size*size/2 (interpolate_twoframe.py:221-222,
- * size=50).  Exact selection (returns an element of the window). */
+ * size=50).  Exact selection (returns an element of the window).  VFI_MEDIAN_PATH (read at every call) picks
+ * the kernel: walk (default), rank or bisect; all three return the same bits. */
 int vfi_median_filter(const float *x, float *y, int N, int H, int W, int size, vfi_stream_t stream);
 
 /* ------------------------------------------------------------------------------------
