@@ -23,6 +23,8 @@
 //   synthesis : row kernel (A cos p, A sin p -> forward row FFT -> T), column kernel (forward column FFT, sum of
 //               rotated, masked band spectra + embedded low-pass of the coarser level); levels without bands only embed
 //               (pyr_combine_kernel).
+//   backward  : vfi_pyr_synthesize_backward, the synthesis' adjoint = the analysis passes with the tables A_k (P_a with the
+//               synthesis' two-sided angle masks), the synthesis' 1/(H W), and a gradient epilogue on (phase, amplitude).
 // All mask tables are precomputed once per plan in double precision, stored in the unshifted (FFT-native)
 // index order so every table read is coalesced with the spectrum access.
 #include "vfi_common.h"
@@ -33,6 +35,7 @@
 #include <cstdlib>
 #include <map>
 #include <new>
+#include <type_traits>
 #include <vector>
 
 namespace {
@@ -47,6 +50,7 @@ struct Level {
     float *P_a;        // [nb][h][w] analysis  : lo0 * prod_{j<k} lomask_j * himask_k * angle mask (one sided), unshifted order
     float *P_s;        // [nb][h][w] synthesis : angle mask (two sided) * himask
     float *lomask;     // [h2][w2]  low-pass applied to the NEXT level's window, unshifted order of that window
+    float *A = nullptr;   // [nb][h][w] synthesis adjoint: lo0 * prod_{j<k} lomask_j * P_s (vfi_pyr_plan_prepare_adjoint)
 };
 
 }  // namespace
@@ -71,6 +75,7 @@ struct vfi_pyr_plan {
     // kept for vfi_pyr_plan_prepare_filter
     std::vector<double> log_rad, xr0, yr, yir;
     std::vector<float *> filters;   // [id] -> H x (W/2+1) radial gain tables
+    bool adjoint = false;           // Level::A built (vfi_pyr_plan_prepare_adjoint)
 };
 
 namespace {
@@ -118,6 +123,43 @@ int dev_alloc(vfi_pyr_plan *p, void **dev, size_t bytes) {
 // shifted-window index (DC at h/2) for an unshifted index u of a length-h axis
 inline int shifted_of(int u, int h) { return (u + h / 2) % h; }
 
+// upstream's angular LUTs: abscissae xc, one-sided analysis mask ya, two-sided synthesis mask ys
+void angle_luts(int nb, std::vector<double> &xc, std::vector<double> &ya, std::vector<double> &ys) {
+    const int lut = 1024, order = nb - 1;
+    const int nl = 3 * lut + 3;
+    xc.resize(nl); ya.resize(nl); ys.resize(nl);
+    double fact_o = 1, fact_2o = 1;
+    for (int i = 2; i <= order; ++i) fact_o *= i;
+    for (int i = 2; i <= 2 * order; ++i) fact_2o *= i;
+    const double cst = std::pow(2.0, 2 * order) * fact_o * fact_o / (nb * fact_2o);
+    for (int i = 0; i < nl; ++i) {
+        xc[i] = kPi * (double)(i - (2 * lut + 1)) / lut;
+        double alpha = std::fmod(xc[i] + kPi, 2 * kPi);
+        if (alpha < 0) alpha += 2 * kPi;
+        alpha -= kPi;
+        const double c = std::pow(std::cos(xc[i]), order);
+        ya[i] = 2.0 * std::sqrt(cst) * c * (std::fabs(alpha) < kPi / 2 ? 1.0 : 0.0);
+        ys[i] = std::sqrt(cst) * c;
+    }
+}
+
+// chain(spos, k) = lo0 * prod_{j<k} lomask_j at the full-grid (shifted) position spos: what the build's running low-pass
+// spectrum has been multiplied by when level k reads it (`lodft = dft * lo0mask`, then `lodft * lomask` per level)
+struct Chain {
+    const vfi_pyr_plan *p;
+    std::vector<std::vector<double>> xr_of;       // xr_of[j] = xr0 - j * log2(scale)
+    explicit Chain(const vfi_pyr_plan *pl) : p(pl), xr_of(pl->nlev + 1, pl->xr0) {
+        const double ls = std::log2(p->scale);
+        for (int j = 1; j <= p->nlev; ++j)
+            for (auto &x : xr_of[j]) x -= j * ls;
+    }
+    double operator()(size_t spos, int k) const {
+        double c = interp(p->log_rad[spos], xr_of[0], p->yir);
+        for (int j = 1; j <= k; ++j) c *= interp(p->log_rad[spos], xr_of[j], p->yir);
+        return c;
+    }
+};
+
 int build_tables(vfi_pyr_plan *p) {
     const int H = p->H, W = p->W, nb = p->nbands;
     const std::vector<double> gy = linspace_grid(H), gx = linspace_grid(W);
@@ -145,23 +187,9 @@ int build_tables(vfi_pyr_plan *p) {
         yr[i] = std::sqrt(yr[i]);
         yir[i] = std::sqrt(std::fabs(1.0 - yr[i] * yr[i]));
     }
-    // angular LUTs
-    const int lut = 1024, order = nb - 1;
-    const int nl = 3 * lut + 3;
-    std::vector<double> xc(nl), ya(nl), ys(nl);
-    double fact_o = 1, fact_2o = 1;
-    for (int i = 2; i <= order; ++i) fact_o *= i;
-    for (int i = 2; i <= 2 * order; ++i) fact_2o *= i;
-    const double cst = std::pow(2.0, 2 * order) * fact_o * fact_o / (nb * fact_2o);
-    for (int i = 0; i < nl; ++i) {
-        xc[i] = kPi * (double)(i - (2 * lut + 1)) / lut;
-        double alpha = std::fmod(xc[i] + kPi, 2 * kPi);
-        if (alpha < 0) alpha += 2 * kPi;
-        alpha -= kPi;
-        const double c = std::pow(std::cos(xc[i]), order);
-        ya[i] = 2.0 * std::sqrt(cst) * c * (std::fabs(alpha) < kPi / 2 ? 1.0 : 0.0);
-        ys[i] = std::sqrt(cst) * c;
-    }
+    std::vector<double> xc, ya, ys;
+    angle_luts(nb, xc, ya, ys);
+    const int nl = (int)xc.size();
     std::vector<double> xcb(nl);
     p->log_rad = log_rad; p->xr0 = xr; p->yr = yr; p->yir = yir;
 
@@ -175,17 +203,8 @@ int build_tables(vfi_pyr_plan *p) {
     int rc;
     if ((rc = dev_upload(p, t, &p->lo0)) || (rc = dev_upload(p, t2, &p->hi0))) return rc;
 
-    // chain(s, k) = lo0 * prod_{j<k} lomask_j at the full-grid (shifted) position s: what the build's running low-pass
-    // spectrum has been multiplied by when level k reads it (`lodft = dft * lo0mask`, then `lodft * lomask` per level)
     const double ls = std::log2(p->scale);
-    std::vector<std::vector<double>> xr_of(p->nlev + 1, p->xr0);      // xr_of[j] = xr0 - j * log2(scale)
-    for (int j = 1; j <= p->nlev; ++j)
-        for (auto &x : xr_of[j]) x -= j * ls;
-    auto chain = [&](size_t spos, int k) {
-        double c = interp(log_rad[spos], xr_of[0], yir);
-        for (int j = 1; j <= k; ++j) c *= interp(log_rad[spos], xr_of[j], yir);
-        return c;
-    };
+    const Chain chain(p);
     for (int k = 0; k < p->nlev; ++k) {
         Level &L = p->lev[k];
         for (auto &x : xr) x -= ls;
@@ -480,6 +499,11 @@ struct RowsPolarArgs {
     unsigned *amp_max;            // analysis only, optional: [groups] bit patterns of the largest amplitude per image group
     int groups;
 };
+// synthesis adjoint rows (vfi_pyr_synthesize_backward): phase / amp receive d phase / d amplitude, inv_hw = 1 / (H W)
+struct RowsPolarGradArgs : RowsPolarArgs {
+    const float *fphase, *famp;   // the forward's (phase, amplitude), same layout (PlaneMap)
+};
+template <bool GRAD> using RowsArgsOf = std::conditional_t<GRAD, RowsPolarGradArgs, RowsPolarArgs>;
 
 template <int NB, bool BLU>
 __global__ __launch_bounds__(kThreads, kThreads / 128) void pyr_level_cols_kernel(const LevelColsArgs a) {
@@ -520,9 +544,11 @@ __device__ __forceinline__ void zero_row_padding(float2 *buf, int lines, int pit
     }
 }
 
-// rows of T -> inverse row FFT -> (phase, amplitude) or the complex coefficient (coeff_to_values, src/train/pyramid.py:63-69)
-template <int NB, bool BLU>
-__device__ __forceinline__ void rows_polar_body(const RowsPolarArgs &a, const int block_x) {
+// rows of T -> inverse row FFT -> (phase, amplitude) or the complex coefficient (coeff_to_values, src/train/pyramid.py:63-69).
+// GRAD: the epilogue of the synthesis adjoint instead -- the coefficient gradient G and the forward's (p, A) at the same
+// offset give d phase = A (Im G cos p - Re G sin p), d amplitude = Re G cos p + Im G sin p.
+template <int NB, bool BLU, bool GRAD = false>
+__device__ __forceinline__ void rows_polar_body(const RowsArgsOf<GRAD> &a, const int block_x) {
     using namespace vfi::fft;
     extern __shared__ float2 buf[];
     const int w = a.pw.n, m = a.pw.m, pitch = padded_length(m);
@@ -555,7 +581,13 @@ __device__ __forceinline__ void rows_polar_body(const RowsPolarArgs &a, const in
         const float2 z = store_value<true>(buf[idx], s.c, blu);
         const float re = z.x * a.inv_hw, im = z.y * a.inv_hw;
         const size_t o = base[l] + j;
-        if (a.pm.complex_coeff) {
+        if constexpr (GRAD) {
+            float sn, cs;
+            sincosf(a.fphase[o], &sn, &cs);      // (as pyr_rows_from_polar_kernel evaluates them for the forward)
+            const float am = a.famp[o];
+            a.phase[o] = am * (im * cs - re * sn);
+            a.amp[o] = re * cs + im * sn;
+        } else if (a.pm.complex_coeff) {
             reinterpret_cast<float2 *>(a.phase)[o] = make_float2(re, im);
         } else {
             const float am = sqrtf(re * re + im * im);
@@ -598,20 +630,23 @@ __device__ __forceinline__ void rows_polar_body(const RowsPolarArgs &a, const in
     }
 }
 
-template <int NB, bool BLU>
-__global__ __launch_bounds__(kThreads, kThreads / 128) void pyr_rows_polar_kernel(const RowsPolarArgs a) {
-    rows_polar_body<NB, BLU>(a, blockIdx.x);
+template <int NB, bool BLU, bool GRAD = false>
+__global__ __launch_bounds__(kThreads, kThreads / 128) void pyr_rows_polar_kernel(const RowsArgsOf<GRAD> a) {
+    rows_polar_body<NB, BLU, GRAD>(a, blockIdx.x);
 }
-struct MultiRowsArgs {
-    RowsPolarArgs lev[kMaxMulti];
+template <class RA>
+struct MultiRowsT {
+    RA lev[kMaxMulti];
     int first[kMaxMulti + 1];
     int count;
 };
-template <int NB, bool BLU>
-__global__ __launch_bounds__(kThreads, kThreads / 128) void pyr_multi_rows_polar_kernel(const MultiRowsArgs ma) {
+using MultiRowsArgs = MultiRowsT<RowsPolarArgs>;
+static_assert(sizeof(MultiRowsT<RowsPolarGradArgs>) <= 4096, "kernel arguments are limited to 4 KiB");
+template <int NB, bool BLU, bool GRAD = false>
+__global__ __launch_bounds__(kThreads, kThreads / 128) void pyr_multi_rows_polar_kernel(const MultiRowsT<RowsArgsOf<GRAD>> ma) {
     int i = 0;
     while (i + 1 < ma.count && (int)blockIdx.x >= ma.first[i + 1]) ++i;      // (uniform)
-    rows_polar_body<NB, BLU>(ma.lev[i], (int)blockIdx.x - ma.first[i]);
+    rows_polar_body<NB, BLU, GRAD>(ma.lev[i], (int)blockIdx.x - ma.first[i]);
 }
 
 __global__ void pyr_amp_max_finish_kernel(const unsigned *__restrict__ bits, float *__restrict__ out, int count, float eps) {
@@ -943,6 +978,43 @@ PlaneMap make_map(const int *plane_index, int level, int N, int nb, int flags) {
 
 inline int blocks_1d(long long n) { long long b = (n + 255) / 256; return (int)(b > 16384 ? 16384 : (b < 1 ? 1 : b)); }
 
+// generic-engine row pass of one level (analysis, or the synthesis adjoint with GRAD)
+template <bool GRAD>
+void launch_level_rows(const RowsArgsOf<GRAD> &ra, hipStream_t s) {
+    const dim3 grid((unsigned)((ra.rows + ra.lines - 1) / ra.lines));
+    const size_t lds = vfi::fft::row_lds_bytes(ra.pw, ra.lines, (size_t)ra.lines * sizeof(size_t));
+    if (ra.pw.bluestein) {
+        allow_big_lds<pyr_rows_polar_kernel<4, true, GRAD>>();
+        hipLaunchKernelGGL((pyr_rows_polar_kernel<4, true, GRAD>), grid, dim3(vfi::fft::kThreads), lds, s, ra);
+    } else {
+        allow_big_lds<pyr_rows_polar_kernel<4, false, GRAD>>();
+        hipLaunchKernelGGL((pyr_rows_polar_kernel<4, false, GRAD>), grid, dim3(vfi::fft::kThreads), lds, s, ra);
+    }
+}
+// the small levels' row passes in one launch; g holds the adjoint's form of every entry (sliced to the analysis form for !GRAD)
+template <bool GRAD>
+void launch_multi_rows(const MultiRowsT<RowsPolarGradArgs> &g, bool blu, size_t lds, hipStream_t s) {
+    MultiRowsT<RowsArgsOf<GRAD>> m;
+    m.count = g.count;
+    for (int i = 0; i <= g.count; ++i) m.first[i] = g.first[i];
+    for (int i = 0; i < g.count; ++i) m.lev[i] = g.lev[i];
+    const dim3 grid(m.first[m.count]);
+    if (blu) {
+        allow_big_lds<pyr_multi_rows_polar_kernel<4, true, GRAD>>();
+        hipLaunchKernelGGL((pyr_multi_rows_polar_kernel<4, true, GRAD>), grid, dim3(vfi::fft::kThreads), lds, s, m);
+    } else {
+        allow_big_lds<pyr_multi_rows_polar_kernel<4, false, GRAD>>();
+        hipLaunchKernelGGL((pyr_multi_rows_polar_kernel<4, false, GRAD>), grid, dim3(vfi::fft::kThreads), lds, s, m);
+    }
+}
+
+// vfi_pyr_synthesize_backward runs the analysis passes on the synthesis' adjoint: the level tables A_k in place of P_a, the
+// 1 / (H W) of the synthesis' final inverse in place of each level's 1 / (h w) (also on the low residual), and with
+// (phase, amplitude) the gradient epilogue of the row pass, which reads the forward's values
+struct Adjoint {
+    const float *const *phase, *const *amp;   // forward inputs per level (unused with VFI_PYR_COMPLEX_COEFF)
+};
+
 }  // namespace
 
 extern "C" int vfi_pyr_plan_create(int H, int W, int height, int nbands, double scale_factor, int max_images,
@@ -1083,7 +1155,8 @@ extern "C" int vfi_pyr_plan_level_size(const vfi_pyr_plan *p, int level, int *h,
 
 static int pyr_analyze_impl(vfi_pyr_plan *p, const float *img, int N, float *high, float *const *phase,
                             float *const *amp, const int *plane_index, float *low, float phase_scale,
-                            unsigned long long level_mask, int flags, float *amp_max, int groups, float eps, vfi_stream_t stream) {
+                            unsigned long long level_mask, int flags, float *amp_max, int groups, float eps, vfi_stream_t stream,
+                            const Adjoint *adj = nullptr) {
     VFI_REQUIRE(p && img, VFI_ERR_INVALID_ARG, "vfi_pyr_analyze: null pointer");
     VFI_REQUIRE(!amp_max || (groups >= 1 && groups <= 4 && !(flags & VFI_PYR_COMPLEX_COEFF)), VFI_ERR_INVALID_ARG,
                 "vfi_pyr_analyze_max: groups must be 1..4 and the outputs (phase, amplitude)");
@@ -1092,6 +1165,8 @@ static int pyr_analyze_impl(vfi_pyr_plan *p, const float *img, int N, float *hig
                 "vfi_pyr_analyze: null phase/amp tables");
     hipStream_t s = vfi::as_stream(stream);
     const int H = p->H, W = p->W, nb = p->nbands;
+    const bool grad = adj && !(flags & VFI_PYR_COMPLEX_COEFF);      // gradient epilogue on (phase, amplitude)
+    const float inv_full = 1.0f / ((float)H * (float)W);
     int rc;
     if (amp_max && hipMemsetAsync(p->amp_bits, 0, sizeof(unsigned) * p->nlev * groups, s) != hipSuccess)
         return vfi::fail(VFI_ERR_LAUNCH, "vfi_pyr_analyze_max: memset");
@@ -1118,7 +1193,7 @@ static int pyr_analyze_impl(vfi_pyr_plan *p, const float *img, int N, float *hig
     if (multi_mask) {
         using namespace vfi::fft;
         MultiColsArgs mc[2];      // [bluestein]
-        MultiRowsArgs mr[2];
+        MultiRowsT<RowsPolarGradArgs> mr[2];
         size_t clds[2] = {0, 0}, rlds[2] = {0, 0};
         for (int b = 0; b < 2; ++b) { mc[b].count = 0; mc[b].first[0] = 0; mr[b].count = 0; mr[b].first[0] = 0; }
         size_t toff = 0;          // (float2 elements into p->bands)
@@ -1127,6 +1202,7 @@ static int pyr_analyze_impl(vfi_pyr_plan *p, const float *img, int N, float *hig
             const Level &L = p->lev[k];
             VFI_REQUIRE(phase[k] && ((flags & VFI_PYR_COMPLEX_COEFF) || amp[k]), VFI_ERR_INVALID_ARG,
                         "vfi_pyr_analyze: null output for level %d", k);
+            VFI_REQUIRE(!grad || (adj->phase[k] && adj->amp[k]), VFI_ERR_INVALID_ARG, "vfi_pyr_synthesize_backward: null input for level %d", k);
             Plan1D ph, pw;
             if ((rc = get_fft(p, L.h, &ph)) || (rc = get_fft(p, L.w, &pw))) return rc;
             float2 *T = p->bands + toff;
@@ -1134,16 +1210,18 @@ static int pyr_analyze_impl(vfi_pyr_plan *p, const float *img, int N, float *hig
             int tile, bpp;
             level_tiling(ph, L.w, &tile, &bpp);
             MultiColsArgs &c = mc[ph.bluestein ? 1 : 0];
-            c.lev[c.count] = LevelColsArgs{ph, p->half0, T, L.P_a, L.h, L.w, H, W, tile, bpp};
+            c.lev[c.count] = LevelColsArgs{ph, p->half0, T, adj ? L.A : L.P_a, L.h, L.w, H, W, tile, bpp};
             c.first[c.count + 1] = c.first[c.count] + 8 * ceil_div(ceil_div(L.w, tile), 8);
             ++c.count;
             clds[ph.bluestein ? 1 : 0] = std::max(clds[ph.bluestein ? 1 : 0], level_lds_bytes(ph, tile, bpp));
             const long long rows = (long long)N * nb * L.h;
             int lines = rows_per_group(pw, rows);
             if (lines > 256) lines = 256;
-            MultiRowsArgs &r = mr[pw.bluestein ? 1 : 0];
-            r.lev[r.count] = RowsPolarArgs{pw, T, phase[k], amp ? amp[k] : nullptr, make_map(plane_index, k, N, nb, flags), rows, L.h, lines,
-                                           1.0f / ((float)L.h * (float)L.w), phase_scale, amp_max ? p->amp_bits + (size_t)k * groups : nullptr, groups};
+            MultiRowsT<RowsPolarGradArgs> &r = mr[pw.bluestein ? 1 : 0];
+            r.lev[r.count] = RowsPolarGradArgs{{pw, T, phase[k], amp ? amp[k] : nullptr, make_map(plane_index, k, N, nb, flags), rows, L.h, lines,
+                                                adj ? inv_full : 1.0f / ((float)L.h * (float)L.w), phase_scale,
+                                                amp_max ? p->amp_bits + (size_t)k * groups : nullptr, groups},
+                                               grad ? adj->phase[k] : nullptr, grad ? adj->amp[k] : nullptr};
             r.first[r.count + 1] = r.first[r.count] + (int)((rows + lines - 1) / lines);
             ++r.count;
             rlds[pw.bluestein ? 1 : 0] = std::max(rlds[pw.bluestein ? 1 : 0], row_lds_bytes(pw, lines, (size_t)lines * sizeof(size_t)));
@@ -1156,21 +1234,21 @@ static int pyr_analyze_impl(vfi_pyr_plan *p, const float *img, int N, float *hig
             allow_big_lds<pyr_multi_level_cols_kernel<4, true>>();
             hipLaunchKernelGGL((pyr_multi_level_cols_kernel<4, true>), dim3(mc[1].first[mc[1].count], N), dim3(kThreads), clds[1], s, mc[1]);
         }
-        if (mr[0].count) {
-            allow_big_lds<pyr_multi_rows_polar_kernel<4, false>>();
-            hipLaunchKernelGGL((pyr_multi_rows_polar_kernel<4, false>), dim3(mr[0].first[mr[0].count]), dim3(kThreads), rlds[0], s, mr[0]);
-        }
-        if (mr[1].count) {
-            allow_big_lds<pyr_multi_rows_polar_kernel<4, true>>();
-            hipLaunchKernelGGL((pyr_multi_rows_polar_kernel<4, true>), dim3(mr[1].first[mr[1].count]), dim3(kThreads), rlds[1], s, mr[1]);
-        }
+        for (int b = 0; b < 2; ++b)
+            if (mr[b].count) {
+                if (grad) launch_multi_rows<true>(mr[b], b == 1, rlds[b], s);
+                else launch_multi_rows<false>(mr[b], b == 1, rlds[b], s);
+            }
     }
     for (int k = 0; k < p->nlev; ++k) {
         const Level &L = p->lev[k];
         if (!((level_mask >> k) & 1ull) || ((multi_mask >> k) & 1ull)) continue;      // (the levels read the half spectrum directly: nothing to pass along)
         VFI_REQUIRE(phase[k] && ((flags & VFI_PYR_COMPLEX_COEFF) || amp[k]), VFI_ERR_INVALID_ARG,
                     "vfi_pyr_analyze: null output for level %d", k);
+        VFI_REQUIRE(!grad || (adj->phase[k] && adj->amp[k]), VFI_ERR_INVALID_ARG, "vfi_pyr_synthesize_backward: null input for level %d", k);
         using namespace vfi::fft;
+        const float *Q = adj ? L.A : L.P_a;
+        const float row_scale = adj ? inv_full : 1.0f / ((float)L.h * (float)L.w);
         Plan1D ph, pw;
         vfi::pyrw::Tables tbh, tbw;
         if ((rc = get_fft(p, L.h, &ph)) || (rc = get_fft(p, L.w, &pw)) || (rc = wave_tables(p, kWaveAnaCols, ph, &tbh)) ||
@@ -1180,13 +1258,13 @@ static int pyr_analyze_impl(vfi_pyr_plan *p, const float *img, int N, float *hig
         const PlaneMap pm = make_map(plane_index, k, N, nb, flags);
         unsigned *amax = amp_max ? p->amp_bits + (size_t)k * groups : nullptr;
         if (tbh.M) {
-            vfi::pyrw::AnaColsArgs ca{tbh, p->half0, W / 2 + 1, H, L.P_a, p->bands, tpitch, N, L.h, L.w};
+            vfi::pyrw::AnaColsArgs ca{tbh, p->half0, W / 2 + 1, H, Q, p->bands, tpitch, N, L.h, L.w};
             if ((rc = vfi::pyrw::launch_ana_cols(ca, s))) return rc;
             debug_scan(p->bands, (size_t)N * nb * L.h * tpitch * 2, s, "T after the wave column pass", k);
         } else {
             int tile, bpp;
             level_tiling(ph, L.w, &tile, &bpp);
-            LevelColsArgs ca{ph, p->half0, p->bands, L.P_a, L.h, L.w, H, W, tile, bpp};
+            LevelColsArgs ca{ph, p->half0, p->bands, Q, L.h, L.w, H, W, tile, bpp};
             const dim3 cgrid(8 * ceil_div(ceil_div(L.w, ca.tile), 8), N);
             const size_t clds = level_lds_bytes(ph, tile, bpp);
             if (ph.bluestein) {
@@ -1199,23 +1277,17 @@ static int pyr_analyze_impl(vfi_pyr_plan *p, const float *img, int N, float *hig
         }
         if (tbw.M) {
             vfi::pyrw::RowsArgs ra{tbw, p->bands, tpitch, phase[k], amp ? amp[k] : nullptr, pm, N * nb, L.h, L.w,
-                                   1.0f / ((float)L.h * (float)L.w), phase_scale, amax, groups};
-            if ((rc = vfi::pyrw::launch_rows_polar(ra, s))) return rc;
+                                   row_scale, phase_scale, amax, groups};
+            if (grad) rc = vfi::pyrw::launch_rows_polar_grad(vfi::pyrw::RowsGradArgs{ra, adj->phase[k], adj->amp[k]}, s);
+            else rc = vfi::pyrw::launch_rows_polar(ra, s);
+            if (rc) return rc;
         } else {
             const long long rows = (long long)N * nb * L.h;
             int lines = rows_per_group(pw, rows);
             if (lines > 256) lines = 256;
-            RowsPolarArgs ra{pw, p->bands, phase[k], amp ? amp[k] : nullptr, pm, rows, L.h, lines,
-                             1.0f / ((float)L.h * (float)L.w), phase_scale, amax, groups};
-            if (pw.bluestein) {
-                allow_big_lds<pyr_rows_polar_kernel<4, true>>();
-                hipLaunchKernelGGL((pyr_rows_polar_kernel<4, true>), dim3((unsigned)((rows + lines - 1) / lines)), dim3(kThreads),
-                                   row_lds_bytes(pw, lines, (size_t)lines * sizeof(size_t)), s, ra);
-            } else {
-                allow_big_lds<pyr_rows_polar_kernel<4, false>>();
-                hipLaunchKernelGGL((pyr_rows_polar_kernel<4, false>), dim3((unsigned)((rows + lines - 1) / lines)), dim3(kThreads),
-                                   row_lds_bytes(pw, lines, (size_t)lines * sizeof(size_t)), s, ra);
-            }
+            RowsPolarArgs ra{pw, p->bands, phase[k], amp ? amp[k] : nullptr, pm, rows, L.h, lines, row_scale, phase_scale, amax, groups};
+            if (grad) launch_level_rows<true>(RowsPolarGradArgs{ra, adj->phase[k], adj->amp[k]}, s);
+            else launch_level_rows<false>(ra, s);
         }
     }
     if (low) {  // low residual: real(ifft2(window(dft) * low_gain))
@@ -1225,7 +1297,7 @@ static int pyr_analyze_impl(vfi_pyr_plan *p, const float *img, int N, float *hig
         if ((rc = fft2d_c2c(p, buf, N, p->hl, p->wl, true, s))) return rc;
         const long long tot = (long long)N * tot1;
         hipLaunchKernelGGL(complex_real_kernel, dim3(blocks_1d(tot)), dim3(256), 0, s, buf, low, tot,
-                           1.0f / ((float)p->hl * (float)p->wl));
+                           adj ? inv_full : 1.0f / ((float)p->hl * (float)p->wl));
     }
     if (high) {  // high residual: C2R of half * hi0 / (H W)
         hipLaunchKernelGGL(pyr_high_kernel, dim3(ceil_div(W / 2 + 1, 256), H), dim3(256), 0, s, p->half0, p->half_hi, p->hi0, N, H, W,
@@ -1340,4 +1412,61 @@ extern "C" int vfi_pyr_synthesize(vfi_pyr_plan *p, const float *high, const floa
     const long long tot = (long long)N * H * W;
     hipLaunchKernelGGL(complex_real_kernel, dim3(blocks_1d(tot)), dim3(256), 0, s, res, img, tot, 1.0f / ((float)H * (float)W));
     return vfi::check_launch("vfi_pyr_synthesize");
+}
+
+// A_k[b] = lo0 * prod_{j<k} lomask_j * himask_k * two-sided angle mask b on level k's window (unshifted order): P_a with the
+// synthesis' angle masks.  The synthesis is real-linear in the band coefficients z_{k,b}; its adjoint applied to a gradient
+// image g is  grad z_{k,b} = 1/(H W) * IFFT2_k,unnormalised( i * window_k(FFT2(g)) * A_k[b] )  -- an analysis level with
+// these tables and the synthesis' final 1/(H W) (conj of the forward's -i is +i, the analysis' rotation).
+extern "C" int vfi_pyr_plan_prepare_adjoint(vfi_pyr_plan *p) {
+    VFI_REQUIRE(p, VFI_ERR_INVALID_ARG, "vfi_pyr_plan_prepare_adjoint: null plan");
+    if (p->adjoint) return VFI_OK;
+    const int H = p->H, W = p->W, nb = p->nbands;
+    const std::vector<double> gy = linspace_grid(H), gx = linspace_grid(W);
+    std::vector<double> xc, ya, ys;
+    angle_luts(nb, xc, ya, ys);
+    std::vector<double> xcb(xc.size()), xr = p->xr0;
+    const double ls = std::log2(p->scale);
+    const Chain chain(p);
+    std::vector<std::vector<float>> tabs(p->nlev);
+    for (int k = 0; k < p->nlev; ++k) {
+        const Level &L = p->lev[k];
+        for (auto &x : xr) x -= ls;
+        const int h = L.h, w = L.w, sy = H / 2 - h / 2, sx = W / 2 - w / 2;
+        std::vector<double> g((size_t)h * w);      // himask_k * chain, as build_tables folds P_a
+        for (int u = 0; u < h; ++u)
+            for (int v = 0; v < w; ++v) {
+                const size_t s = (size_t)(sy + shifted_of(u, h)) * W + (sx + shifted_of(v, w));
+                g[(size_t)u * w + v] = (double)(float)interp(p->log_rad[s], xr, p->yr) * chain(s, k);
+            }
+        std::vector<float> &a = tabs[k];
+        a.resize((size_t)nb * h * w);
+        for (int b = 0; b < nb; ++b) {
+            for (size_t i = 0; i < xc.size(); ++i) xcb[i] = xc[i] + kPi * b / nb;
+            for (int u = 0; u < h; ++u)
+                for (int v = 0; v < w; ++v) {
+                    const int i = sy + shifted_of(u, h), j = sx + shifted_of(v, w);
+                    a[((size_t)b * h + u) * w + v] = (float)((double)(float)interp(std::atan2(gy[i], gx[j]), xcb, ys) * g[(size_t)u * w + v]);
+                }
+        }
+    }
+    for (int k = 0; k < p->nlev; ++k) {
+        const int rc = dev_upload(p, tabs[k], &p->lev[k].A);
+        if (rc) return vfi::fail(rc, "vfi_pyr_plan_prepare_adjoint: device allocation / upload failed");
+    }
+    p->adjoint = true;
+    return VFI_OK;
+}
+
+extern "C" int vfi_pyr_synthesize_backward(vfi_pyr_plan *p, const float *grad_img, int N, const float *const *phase,
+                                           const float *const *amp, const int *plane_index, unsigned long long level_mask,
+                                           int flags, float *grad_high, float *const *grad_phase, float *const *grad_amp,
+                                           float *grad_low, vfi_stream_t stream) {
+    VFI_REQUIRE(p && grad_img, VFI_ERR_INVALID_ARG, "vfi_pyr_synthesize_backward: null pointer");
+    VFI_REQUIRE(p->adjoint, VFI_ERR_INVALID_ARG, "vfi_pyr_synthesize_backward: call vfi_pyr_plan_prepare_adjoint first");
+    VFI_REQUIRE((flags & VFI_PYR_COMPLEX_COEFF) || level_mask == 0 || (phase && amp), VFI_ERR_INVALID_ARG,
+                "vfi_pyr_synthesize_backward: null forward phase/amp tables");
+    const Adjoint adj{phase, amp};
+    return pyr_analyze_impl(p, grad_img, N, grad_high, grad_phase, grad_amp, plane_index, grad_low, 1.0f, level_mask, flags,
+                            nullptr, 1, 0.0f, stream, &adj);
 }

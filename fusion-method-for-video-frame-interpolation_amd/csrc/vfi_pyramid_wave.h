@@ -36,6 +36,11 @@ struct RowsArgs {
     int groups;
 };
 
+// synthesis adjoint rows (vfi_pyr_synthesize_backward): `phase` / `amp` receive d phase / d amplitude; inv_hw = 1 / (H W)
+struct RowsGradArgs : RowsArgs {
+    const float *fphase, *famp;   // the forward's (phase, amplitude) planes, same layout (PlaneMap)
+};
+
 // analysis columns: T[n][b] = IFFT_cols( i * window_k(S[n]) * Q[b] )
 struct AnaColsArgs {
     Tables tb;                    // tb.n == h
@@ -85,6 +90,7 @@ int syn_twiddles(int M, float2 *out, int cap);      // synthesis column pass (sa
 
 int launch_rows_polar(const RowsArgs &a, hipStream_t s);        // analysis rows  (coeff_to_values, src/train/pyramid.py:63-69)
 int launch_rows_from_polar(const RowsArgs &a, hipStream_t s);   // synthesis rows (values_to_coeff, src/train/pyramid.py:99-107)
+int launch_rows_polar_grad(const RowsGradArgs &a, hipStream_t s);   // synthesis adjoint rows (vfi_pyrw_rows_grad.hip)
 int launch_ana_cols(const AnaColsArgs &a, hipStream_t s);
 int launch_syn_cols(const SynColsArgs &a, hipStream_t s);
 // supported (load, store, direction): (real, half, forward) = R2C rows, (half, real, inverse) = C2R rows, (complex, complex, *)

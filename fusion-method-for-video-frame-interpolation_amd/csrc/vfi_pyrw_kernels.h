@@ -14,6 +14,7 @@
 // Roofline: HBM -- per coefficient 8 B of T written and read once plus the 8 B of (phase, amplitude).
 #pragma once
 #include <mutex>
+#include <type_traits>
 #include "vfi_pyramid_wave.h"
 #include "vfi_wfft.h"
 #include "vfi_wfft_configs.h"
@@ -118,8 +119,11 @@ __device__ __forceinline__ void transform(float2 (&v)[C::E], int lane, const Lds
 // =====================================================================================================================
 // rows: a batch = L consecutive rows of ONE plane (so every descriptor of a batch is wave-uniform)
 // =====================================================================================================================
-template <class C, bool BLU>
-__global__ __launch_bounds__(C::TEAM > 64 ? C::TEAM : kMaxThreads, 2) void rows_polar_kernel(const RowsArgs a) {
+// GRAD (vfi_pyr_synthesize_backward): the rows are the synthesis' adjoint applied to a gradient image, and the epilogue turns
+// the coefficient gradient G into (d phase, d amplitude) = (A (Im G cos p - Re G sin p), Re G cos p + Im G sin p) with the
+// forward's (p, A), read at the offsets it writes.  The analysis instantiations (GRAD = false) compile as before.
+template <class C, bool BLU, bool GRAD = false>
+__global__ __launch_bounds__(C::TEAM > 64 ? C::TEAM : kMaxThreads, 2) void rows_polar_kernel(const std::conditional_t<GRAD, RowsGradArgs, RowsArgs> a) {
     using I = Io<C>;
     extern __shared__ float2 lds[];
     const int lane = threadIdx.x % C::TEAM, wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x / C::TEAM)), nw = blockDim.x / C::TEAM;   // (wave = index of this lane's team)
@@ -153,7 +157,7 @@ __global__ __launch_bounds__(C::TEAM > 64 ? C::TEAM : kMaxThreads, 2) void rows_
         transform<C, BLU>(v, lane, m);
         const size_t obase = ((size_t)(m.ints[img] + band * a.pm.band_stride) * h + y0) * n;
         const int grp = img % a.groups;
-        if (a.pm.complex_coeff) {
+        if (!GRAD && a.pm.complex_coeff) {
             const rsrc_t rC = rsrc_of(reinterpret_cast<float2 *>(a.phase) + obase);
 #pragma unroll
             for (int q = 0; q < I::QL; ++q) {
@@ -168,6 +172,31 @@ __global__ __launch_bounds__(C::TEAM > 64 ? C::TEAM : kMaxThreads, 2) void rows_
                     const float2 z = fft::store_value<true>(v[q * I::RL + r], BLU ? m.ch[pos] : make_float2(0.0f, 0.0f), BLU);
                     const unsigned vo = ok && (!BLU || pos < n) ? (unsigned)(l * n + k) * 8u : kOob;
                     st2(rC, vo, r * I::PL * 8, make_float2(z.x * a.inv_hw, z.y * a.inv_hw));
+                }
+            }
+        } else if constexpr (GRAD) {
+            const rsrc_t rP = rsrc_of(a.phase + obase), rA = rsrc_of(a.amp + obase);
+            const rsrc_t rFP = rsrc_of(a.fphase + obase), rFA = rsrc_of(a.famp + obase);
+#pragma unroll
+            for (int q = 0; q < I::QL; ++q) {
+                int l, k;
+                bool ok;
+                lane_index<C, I::SL>(lane, q, l, k, ok);
+                ok = ok && y0 + l < h;
+#pragma unroll
+                for (int r = 0; r < I::RL; ++r) {
+                    if (BLU && r >= I::RL_BLU) continue;
+                    const int pos = k + r * I::PL;
+                    const float2 z = fft::store_value<true>(v[q * I::RL + r], BLU ? m.ch[pos] : make_float2(0.0f, 0.0f), BLU);
+                    const float re = z.x * a.inv_hw, im = z.y * a.inv_hw;
+                    const unsigned vo = ok && (!BLU || pos < n) ? (unsigned)(l * n + k) * 4u : kOob;
+                    // sin / cos as rows_from_polar_kernel evaluates them for the forward (phase reduced to [-0.5, 0.5] revolutions)
+                    float rev = ld1(rFP, vo, r * I::PL * 4) * 0.15915494309189535f;
+                    rev -= rintf(rev);
+                    const float sn = __builtin_amdgcn_sinf(rev), cs = __builtin_amdgcn_cosf(rev);
+                    const float am = ld1(rFA, vo, r * I::PL * 4);
+                    st1(rP, vo, r * I::PL * 4, am * (im * cs - re * sn));
+                    st1(rA, vo, r * I::PL * 4, re * cs + im * sn);
                 }
             }
         } else {

@@ -65,6 +65,9 @@ SIGNATURES = {
                             c_fl, ctypes.c_ulonglong, c_i, c_f, c_i, c_fl, c_s],
     "vfi_pyr_synthesize": [ctypes.c_void_p, c_f, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, c_f,
                            ctypes.c_ulonglong, c_i, c_f, c_i, c_s],
+    "vfi_pyr_plan_prepare_adjoint": [ctypes.c_void_p],
+    "vfi_pyr_synthesize_backward": [ctypes.c_void_p, c_f, c_i, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                    ctypes.c_ulonglong, c_i, c_f, ctypes.c_void_p, ctypes.c_void_p, c_f, c_s],
 }
 # entry points that return a value instead of a vfi_status
 RESTYPES = {"vfi_conv2d_packed_floats": c_l}

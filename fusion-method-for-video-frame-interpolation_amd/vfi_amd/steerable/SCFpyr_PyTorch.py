@@ -5,10 +5,14 @@ coeff = [hi (N,H,W), [nbands x (N,h,w,2)] per level finest first, lo (N,hL,wL)] 
 
 Backed by one plan per (H, W) in libvfi_hip.so (level geometry, mask tables, the tables of the hand-written FFT
 engines -- no FFT library is linked --, workspace).
+
+`reconstruct` (and `vfi_amd.train.Pyramid.inv_filter`) is differentiable with respect to its inputs: when grad mode is on
+and an input requires grad it runs as the autograd node `Synthesis`, whose backward is vfi_pyr_synthesize_backward.
 """
 import ctypes
 
 import torch
+from torch.autograd.function import once_differentiable
 
 from .. import _lib
 from .._lib import VfiLibraryError
@@ -103,6 +107,25 @@ class Plan:
                   out.data_ptr(), _lib.stream_ptr(), work=("byte", 12.0 * n * self.h * self.w, "pyr_band_filter_pair"))
         return out
 
+    def synthesize_backward(self, grad_img, phase, amp, table, mask, flags, grad_high, grad_phase, grad_amp, grad_low):
+        """Gradients of `synthesize` for the loss gradient grad_img (N,H,W): arguments in synthesize's layout; grad_phase
+        receives interleaved (re, im) gradients with COMPLEX_COEFF.  Builds the plan's adjoint tables on first use."""
+        if not getattr(self, "_adjoint", False):
+            with torch.cuda.device(self.device):
+                _lib.call("vfi_pyr_plan_prepare_adjoint", self._h)
+            self._adjoint = True
+        n = grad_img.shape[0]
+        tab = (ctypes.c_int * len(table))(*table) if table is not None else None
+        polar = not flags & COMPLEX_COEFF
+        reads = 4.0 * n * sum(2 * self.nbands * a * b for k, (a, b) in enumerate(self.sizes[:-1]) if (mask >> k) & 1) if polar else 0.0
+        _lib.call("vfi_pyr_synthesize_backward", self._h, _lib.dptr(grad_img, "grad_img"), n,
+                  _ptr_array(phase) if phase is not None else None, _ptr_array(amp) if amp is not None else None, tab, mask, flags,
+                  grad_high.data_ptr() if torch.is_tensor(grad_high) else None, _ptr_array(grad_phase),
+                  _ptr_array(grad_amp) if grad_amp is not None else None, grad_low.data_ptr() if torch.is_tensor(grad_low) else None,
+                  _lib.stream_ptr(),
+                  work=("byte", self._bytes(n, mask, torch.is_tensor(grad_high), torch.is_tensor(grad_low)) + reads,
+                        "pyr_synthesize_backward"))
+
     def synthesize(self, high, phase, amp, table, low, mask, flags, img):
         n = img.shape[0]
         tab = (ctypes.c_int * len(table))(*table) if table is not None else None
@@ -110,6 +133,69 @@ class Plan:
                   _ptr_array(phase), _ptr_array(amp) if amp is not None else None, tab,
                   low.data_ptr() if torch.is_tensor(low) else None, mask, flags, img.data_ptr(), n, _lib.stream_ptr(),
                   work=("byte", self._bytes(n, mask, torch.is_tensor(high), torch.is_tensor(low)), "pyr_synthesize"))
+
+
+class Synthesis(torch.autograd.Function):
+    """The pyramid's synthesis as an autograd node.  `layout` maps the flat inputs to the library's arguments:
+    layout.forward(inputs) -> image, layout.backward(grad, inputs, needs) -> one gradient (or None) per input.  Inputs that
+    are not tensors (the scalar 0 the reference uses for a missing level) get None."""
+
+    @staticmethod
+    def forward(ctx, layout, *inputs):
+        ctx.layout = layout
+        ctx.is_tensor = [torch.is_tensor(t) for t in inputs]
+        ctx.save_for_backward(*[t for t in inputs if torch.is_tensor(t)])
+        return layout.forward(inputs)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad):
+        saved = iter(ctx.saved_tensors)
+        inputs = [next(saved) if t else 0 for t in ctx.is_tensor]
+        needs = [bool(nd and t) for nd, t in zip(ctx.needs_input_grad[1:], ctx.is_tensor)]
+        if not any(needs):
+            return (None,) * (1 + len(inputs))
+        return (None,) + tuple(ctx.layout.backward(grad.contiguous(), inputs, needs))
+
+
+def wants_grad(inputs):
+    """Whether a synthesis over `inputs` has to be recorded for autograd."""
+    return torch.is_grad_enabled() and any(torch.is_tensor(t) and t.requires_grad for t in inputs)
+
+
+class _ComplexLayout:
+    """reconstruct's inputs, flattened: hi (N,H,W), nlev x nb band coefficients (N,h,w,2) finest first, lo (N,hL,wL)."""
+
+    def __init__(self, plan, nlev, nb):
+        self.plan, self.nlev, self.nb = plan, nlev, nb
+
+    def forward(self, inputs):
+        nb = self.nb
+        hi, lo = inputs[0].contiguous(), inputs[-1].contiguous()
+        n, h, w = hi.shape
+        bands = [torch.stack([b.contiguous() for b in inputs[1 + k * nb:1 + (k + 1) * nb]], 0) for k in range(self.nlev)]   # (nb, N, h, w, 2)
+        img = torch.empty((n, h, w), dtype=torch.float32, device=hi.device)
+        self.plan.synthesize(hi, bands, None, None, lo, (1 << self.nlev) - 1, BAND_MAJOR | COMPLEX_COEFF, img)
+        return img
+
+    def backward(self, grad, inputs, needs):
+        nb, plan = self.nb, self.plan
+        n = grad.shape[0]
+        new = lambda *s: torch.empty(s, dtype=torch.float32, device=grad.device)
+        mask, gb = 0, []
+        for k in range(self.nlev):
+            if any(needs[1 + k * nb:1 + (k + 1) * nb]):
+                mask |= 1 << k
+                gb.append(new(nb, n, *plan.sizes[k], 2))
+            else:
+                gb.append(0)
+        gh = new(*grad.shape) if needs[0] else None
+        gl = new(n, *plan.sizes[self.nlev]) if needs[-1] else None
+        plan.synthesize_backward(grad, None, None, None, mask, BAND_MAJOR | COMPLEX_COEFF, gh, gb, None, gl)
+        out = [gh]
+        for k in range(self.nlev):
+            out += [gb[k][b] if needs[1 + k * nb + b] else None for b in range(nb)]
+        return out + [gl]
 
 
 class SCFpyr_PyTorch(object):
@@ -145,10 +231,9 @@ class SCFpyr_PyTorch(object):
         nb = self.nbands
         if nb != len(coeff[1]):
             raise Exception("Unmatched number of orientations")
-        hi, lo = coeff[0].contiguous(), coeff[-1].contiguous()
-        n, h, w = hi.shape
-        plan = self.plan(h, w, n)
-        bands = [torch.stack([b.contiguous() for b in level], 0) for level in coeff[1:-1]]   # (nb, N, h, w, 2)
-        img = torch.empty((n, h, w), dtype=torch.float32, device=hi.device)
-        plan.synthesize(hi, bands, None, None, lo, (1 << len(bands)) - 1, BAND_MAJOR | COMPLEX_COEFF, img)
-        return img
+        n, h, w = coeff[0].shape
+        layout = _ComplexLayout(self.plan(h, w, n), len(coeff) - 2, nb)
+        inputs = [coeff[0]] + [b for level in coeff[1:-1] for b in level] + [coeff[-1]]
+        if wants_grad(inputs):
+            return Synthesis.apply(layout, *inputs)
+        return layout.forward(inputs)

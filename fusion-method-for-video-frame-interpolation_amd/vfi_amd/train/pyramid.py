@@ -13,6 +13,10 @@ Extensions used by this package's own per-frame driver (not in the reference sur
   * entries of `vals.phase/amplitude` (or high_level / low_level) that are not tensors (the scalar 0 the
     reference itself uses for missing levels, src/phase_net/phase_net.py:91-93) are treated as zeros and
     their transforms are skipped.
+
+`inv_filter` is differentiable with respect to high_level, phase, amplitude and low_level (the reference's PhaseNet
+training backpropagates its L1 term through it, src/phase_net/architecture.py:69, src/train/loss.py:5-25): with grad mode
+on and an input that requires grad it runs as the autograd node `Synthesis` (vfi_pyr_synthesize_backward).
 """
 import ctypes
 import math
@@ -21,7 +25,7 @@ import torch
 
 from .. import _lib
 from .._lib import VfiLibraryError
-from ..steerable.SCFpyr_PyTorch import SCFpyr_PyTorch
+from ..steerable.SCFpyr_PyTorch import SCFpyr_PyTorch, Synthesis, wants_grad
 from ..values import DecompValues
 
 __all__ = ["DecompValues", "Pyramid"]
@@ -135,27 +139,67 @@ class Pyramid:
             k0 = next(k for k, p in enumerate(vals.phase) if torch.is_tensor(p))
             n = vals.phase[k0].shape[0] // nb
             h, w = self._full_size
-        plan = self.pyr.plan(h, w, n)
-        mask = 0
-        phase, amp = [], []
-        for k in range(nlev):
-            p, a = vals.phase[k], vals.amplitude[k]
-            if torch.is_tensor(p) and torch.is_tensor(a):
-                if tuple(p.shape) != (n * nb, 1, *plan.sizes[k]):
-                    raise VfiLibraryError(f"inv_filter: level {k} has shape {tuple(p.shape)}, expected "
-                                          f"{(n * nb, 1, *plan.sizes[k])}")
-                mask |= 1 << k
-                phase.append(p.contiguous()); amp.append(a.contiguous())
-            else:
-                phase.append(None); amp.append(None)
-        high = vals.high_level.contiguous() if torch.is_tensor(vals.high_level) else None
-        low = vals.low_level.contiguous() if torch.is_tensor(vals.low_level) else None
-        img = torch.empty((n, h, w), dtype=torch.float32, device=tensors[0].device)
-        plan.synthesize(high, phase, amp, None, low, mask, 0, img)
-        return img
+        layout = _PolarLayout(self.pyr.plan(h, w, n), n, h, w, nlev, nb)
+        inputs = [vals.high_level, *vals.phase, *vals.amplitude, vals.low_level]
+        if wants_grad(inputs):
+            return Synthesis.apply(layout, *inputs)
+        return layout.forward(inputs)
 
     _full_size = None
 
     def set_full_size(self, h, w):
         """Only needed to invert values whose high_level was dropped (no tensor carries H, W)."""
         self._full_size = (h, w)
+
+
+class _PolarLayout:
+    """inv_filter's inputs, flattened: high (N,1,H,W), phase[0..L-1], amplitude[0..L-1] ((N*nb,1,h,w) finest first),
+    low (N,1,hL,wL); any of them may be a non-tensor (zeros).  A level is synthesised when both its planes are tensors."""
+
+    def __init__(self, plan, n, h, w, nlev, nb):
+        self.plan, self.n, self.h, self.w, self.nlev, self.nb = plan, n, h, w, nlev, nb
+
+    def _split(self, inputs):
+        return inputs[0], inputs[1:1 + self.nlev], inputs[1 + self.nlev:1 + 2 * self.nlev], inputs[-1]
+
+    def _levels(self, phase, amp):
+        mask, ps, am = 0, [], []
+        for k in range(self.nlev):
+            p, a = phase[k], amp[k]
+            if torch.is_tensor(p) and torch.is_tensor(a):
+                if tuple(p.shape) != (self.n * self.nb, 1, *self.plan.sizes[k]):
+                    raise VfiLibraryError(f"inv_filter: level {k} has shape {tuple(p.shape)}, expected "
+                                          f"{(self.n * self.nb, 1, *self.plan.sizes[k])}")
+                mask |= 1 << k
+                ps.append(p.contiguous()); am.append(a.contiguous())
+            else:
+                ps.append(None); am.append(None)
+        return mask, ps, am
+
+    def forward(self, inputs):
+        high, phase, amp, low = self._split(inputs)
+        mask, phase, amp = self._levels(phase, amp)
+        high = high.contiguous() if torch.is_tensor(high) else None
+        low = low.contiguous() if torch.is_tensor(low) else None
+        device = next(t for t in inputs if torch.is_tensor(t)).device
+        img = torch.empty((self.n, self.h, self.w), dtype=torch.float32, device=device)
+        self.plan.synthesize(high, phase, amp, None, low, mask, 0, img)
+        return img
+
+    def backward(self, grad, inputs, needs):
+        L = self.nlev
+        high, phase, amp, low = self._split(inputs)
+        mask, phase, amp = self._levels(phase, amp)
+        new = lambda *s: torch.empty(s, dtype=torch.float32, device=grad.device)
+        gp, ga = [], []
+        for k in range(L):
+            if (mask >> k) & 1 and (needs[1 + k] or needs[1 + L + k]):
+                gp.append(new(*phase[k].shape)); ga.append(new(*amp[k].shape))
+            else:
+                mask &= ~(1 << k)
+                gp.append(None); ga.append(None)
+        gh = new(self.n, 1, self.h, self.w) if needs[0] else None
+        gl = new(self.n, 1, *self.plan.sizes[L]) if needs[-1] else None
+        self.plan.synthesize_backward(grad, phase, amp, None, mask, 0, gh, gp, ga, gl)
+        return [gh] + [g if nd else None for g, nd in zip(gp, needs[1:1 + L])] + \
+            [g if nd else None for g, nd in zip(ga, needs[1 + L:1 + 2 * L])] + [gl]

@@ -357,6 +357,24 @@ int vfi_pyr_synthesize(vfi_pyr_plan *plan, const float *high, const float *const
                        const float *const *amp, const int *plane_index, const float *low,
                        unsigned long long level_mask, int flags, float *img, int N, vfi_stream_t stream);
 
+/* Gradient of vfi_pyr_synthesize with respect to its inputs, for training through Pyramid.inv_filter /
+ * SCFpyr_PyTorch.reconstruct.  The synthesis is real-linear in the band coefficients, so its adjoint applied to the
+ * gradient image is an analysis: grad z_{k,b} = 1/(H W) * unnormalised IFFT2_k(i * window_k(FFT2(g)) * A_k[b]) with
+ * A_k[b] = lo0 * prod_{j<k} lomask_j * himask_k * (two-sided) angle mask b; grad high = the analysis' high output of g;
+ * grad low = hL wL / (H W) * the analysis' low output of g.
+ * vfi_pyr_plan_prepare_adjoint builds the A_k tables once per plan (allocates nbands floats per band coefficient of
+ * every level; a second call is a no-op).  vfi_pyr_synthesize_backward returns VFI_ERR_INVALID_ARG without them.
+ *   grad_img  (N, H, W): gradient of the loss with respect to vfi_pyr_synthesize's img
+ *   phase, amp: the forward's inputs (same layout as vfi_pyr_synthesize; unused with VFI_PYR_COMPLEX_COEFF)
+ *   grad_phase[k], grad_amp[k]: d phase = A (Im G cos p - Re G sin p), d amplitude = Re G cos p + Im G sin p for the
+ *          coefficient gradient G; with VFI_PYR_COMPLEX_COEFF grad_phase[k] receives G as interleaved (re, im)
+ *   levels whose level_mask bit is clear, and NULL grad_high / grad_low, are skipped. */
+int vfi_pyr_plan_prepare_adjoint(vfi_pyr_plan *plan);
+int vfi_pyr_synthesize_backward(vfi_pyr_plan *plan, const float *grad_img, int N, const float *const *phase,
+                                const float *const *amp, const int *plane_index, unsigned long long level_mask, int flags,
+                                float *grad_high, float *const *grad_phase, float *const *grad_amp, float *grad_low,
+                                vfi_stream_t stream);
+
 /* ------------------------------------------------------------------------------------
  * Image-space stages the reference runs on the host CPU (skimage / scipy round trips)
  * ---------------------------------------------------------------------------------- */
