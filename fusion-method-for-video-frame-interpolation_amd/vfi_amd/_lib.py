@@ -68,9 +68,17 @@ SIGNATURES = {
     "vfi_pyr_plan_prepare_adjoint": [ctypes.c_void_p],
     "vfi_pyr_synthesize_backward": [ctypes.c_void_p, c_f, c_i, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                     ctypes.c_ulonglong, c_i, c_f, ctypes.c_void_p, ctypes.c_void_p, c_f, c_s],
+    "vfi_conv2d_backward_weight_workspace_floats": [c_i] * 3,
+    "vfi_conv2d_backward_weight": [c_f, c_l, c_f, c_l, c_f, c_f] + [c_i] * 7 + [c_f, c_l, c_s],
+    "vfi_conv2d_backward_data_workspace_floats": [c_i] * 7,
+    "vfi_conv2d_backward_data": [c_f, c_l, c_f, c_f, c_l] + [c_i] * 7 + [c_f, c_l, c_s],
+    "vfi_tanh_residual_clamp_backward": [c_f] * 5 + [c_l, c_s],
+    "vfi_pool2_max_backward": [c_f, c_l] * 4 + [c_i] * 4 + [c_s],
+    "vfi_resize_bilinear_backward": [c_f, c_l] * 3 + [c_i] * 7 + [c_s],
 }
 # entry points that return a value instead of a vfi_status
-RESTYPES = {"vfi_conv2d_packed_floats": c_l}
+RESTYPES = {"vfi_conv2d_packed_floats": c_l, "vfi_conv2d_backward_weight_workspace_floats": c_l,
+            "vfi_conv2d_backward_data_workspace_floats": c_l}
 
 _lock = threading.Lock()
 _lib = None

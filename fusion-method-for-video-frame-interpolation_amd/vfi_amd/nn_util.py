@@ -61,9 +61,16 @@ class PackedModule(nn.Module):
     def __init__(self):
         super().__init__()
         self._packed = None
+        self._packed_key = None
 
     def _invalidate(self):
         self._packed = None
+        self._packed_key = None
+
+    def _param_key(self):
+        """The parameters' identities and in-place version counters: an optimiser step (or any in-place write) bumps
+        `_version`, so the cache notices it without a hook."""
+        return tuple((id(p), p._version) for p in self.parameters())
 
     def load_state_dict(self, *a, **k):
         r = super().load_state_dict(*a, **k)
@@ -85,10 +92,15 @@ class PackedModule(nn.Module):
         modules are shared by frames in flight on other streams (bench.py, interpolate_video): the build therefore ends
         with a host wait for that stream, once per parameter load, so every later caller on ANY stream finds finished
         buffers (no per-call events; never happens inside a hipGraph capture because a captured frame is warmed up
-        first).  `prepare()` is the explicit spelling for callers that want the cost up front."""
-        if self._packed is None:
+        first).  `prepare()` is the explicit spelling for callers that want the cost up front.
+        The cache is keyed on the parameters' version counters as well, so an in-place update (`opt.step()`) rebuilds
+        it at the next call: in training that costs the pack kernels plus one stream sync per step."""
+        key = self._param_key()
+        if self._packed is None or key != self._packed_key:
+            self._packed = None
             with torch.no_grad():
                 self._packed = self._build_packed()
+            self._packed_key = key
             dev = next(self.parameters()).device
             if dev.type == "cuda":
                 torch.cuda.current_stream(dev).synchronize()

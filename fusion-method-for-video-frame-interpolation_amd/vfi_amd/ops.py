@@ -265,6 +265,98 @@ def tanh_residual_clamp(x, base):
     return out
 
 
+def packed_transposed(weight):
+    """PackedConv of W.transpose(0,1).flip(2,3) (no bias): the weights vfi_conv2d_backward_data convolves dY with."""
+    return PackedConv(weight.detach().transpose(0, 1).flip(2, 3))
+
+
+def conv2d_backward_weight(x, dy, ks, pad_mode="zeros", bias=True):
+    """(dW (Cout, Cin, KS, KS), dbias (Cout) or None) of a stride-1 conv2d layer with input x and output gradient dy.
+    One vfi_conv2d_backward_weight call (split-K partial slabs in the per-stream workspace, fixed-order reduction)."""
+    n, cin, h, w = x.shape
+    cout = dy.shape[1]
+    if tuple(dy.shape) != (n, cout, h, w):
+        raise VfiLibraryError(f"conv2d_backward_weight: dy {tuple(dy.shape)} does not match x {tuple(x.shape)}")
+    dw = torch.empty((cout, cin, ks, ks), dtype=torch.float32, device=x.device)
+    db = torch.empty(cout, dtype=torch.float32, device=x.device) if bias else None
+    xp, xs = _slice_ptr(x, "x")
+    gp, gs = _slice_ptr(dy, "dy")
+    ws = _workspace(x.device)
+    work = ("flop", 2.0 * n * cin * cout * ks * ks * h * w, f"conv_wgrad_kernel<{ks}>") if _lib.PROFILE is not None else None
+    _lib.call("vfi_conv2d_backward_weight", xp, xs, gp, gs, dw.data_ptr(), db.data_ptr() if bias else None, n, cin, h, w,
+              cout, ks, PAD[pad_mode], ws.data_ptr(), ws.numel(), _lib.stream_ptr(), work=work)
+    return dw, db
+
+
+BWD_DATA_SPLITK_FLOATS = 8 * 1024 * 1024     # handed on to vfi_conv2d's split-K beyond the embed / fold buffers
+
+
+def conv2d_backward_data(dy, pct, pad_mode="zeros", out=None):
+    """dX (N, Cin, H, W) of a stride-1 conv2d layer from its output gradient dy; `pct` = packed_transposed(weight).
+    One vfi_conv2d_backward_data call; reflect padding takes a workspace of the padded extent, allocated here."""
+    n, cout, h, w = dy.shape
+    cin, ks = pct.cout, pct.ks
+    if pct.cin != cout:
+        raise VfiLibraryError(f"conv2d_backward_data: dy has {cout} channels, weights expect {pct.cin}")
+    if out is None:
+        out = new((n, cin, h, w), dy)
+    elif tuple(out.shape) != (n, cin, h, w):
+        raise VfiLibraryError(f"conv2d_backward_data: out shape {tuple(out.shape)} != {(n, cin, h, w)}")
+    need = _lib.lib().vfi_conv2d_backward_data_workspace_floats(n, cin, h, w, cout, ks, PAD[pad_mode])
+    if need < 0:
+        raise VfiLibraryError(f"conv2d_backward_data: unsupported layer {cout}->{cin} KS={ks}")
+    ws = _workspace(dy.device) if need == 0 else torch.empty(need + BWD_DATA_SPLITK_FLOATS, dtype=torch.float32,
+                                                             device=dy.device)
+    gp, gs = _slice_ptr(dy, "dy")
+    op, os_ = _slice_ptr(out, "out")
+    work = None
+    if _lib.PROFILE is not None:
+        p = (ks - 1) // 2 if pad_mode == "reflect" else 0
+        work = ("flop", 2.0 * n * cin * cout * ks * ks * (h + 2 * p) * (w + 2 * p), f"conv_dgrad<{ks}>")
+    _lib.call("vfi_conv2d_backward_data", gp, gs, pct.packed.data_ptr(), op, os_, n, cin, h, w, cout, ks, PAD[pad_mode],
+              ws.data_ptr(), ws.numel(), _lib.stream_ptr(), work=work)
+    return out
+
+
+def tanh_residual_clamp_backward(x, base, grad, need_x=True, need_base=True):
+    """(grad_x, grad_base) of tanh_residual_clamp; an output not needed is None (not written)."""
+    gx = torch.empty_like(x) if need_x else None
+    gb = torch.empty_like(x) if need_base else None
+    _lib.call("vfi_tanh_residual_clamp_backward", _lib.dptr(x, "x"), _lib.dptr(base, "base"), _lib.dptr(grad, "grad"),
+              gx.data_ptr() if need_x else None, gb.data_ptr() if need_base else None, x.numel(), _lib.stream_ptr(),
+              work=("byte", 20.0 * x.numel(), "tanh_residual_clamp_backward") if _lib.PROFILE is not None else None)
+    return gx, gb
+
+
+def pool2_max_backward(y, grad_pooled, grad_skip=None, out=None):
+    """Gradient of y = relu(z) feeding MaxPool2d(2) and a skip: (max-pool routing of grad_pooled + grad_skip) * [y > 0]."""
+    n, c, h, w = y.shape
+    if out is None:
+        out = new((n, c, h, w), y)
+    yp, ys = _slice_ptr(y, "y")
+    pp, ps = _slice_ptr(grad_pooled, "grad_pooled")
+    kp, ks = (None, 0) if grad_skip is None else _slice_ptr(grad_skip, "grad_skip")
+    op, os_ = _slice_ptr(out, "out")
+    _lib.call("vfi_pool2_max_backward", yp, ys, pp, ps, kp, ks, op, os_, n, c, h, w, _lib.stream_ptr(),
+              work=("byte", 4.0 * n * c * h * w * (2.25 + (grad_skip is not None)), "pool2_max_backward")
+              if _lib.PROFILE is not None else None)
+    return out
+
+
+def resize_bilinear_backward(x, grad, relu_input=True, out=None):
+    """Gradient of x through resize_bilinear(x, 2x size, align_corners=False, relu_input) (gather form)."""
+    n, c, h, w = x.shape
+    if out is None:
+        out = new((n, c, h, w), x)
+    xp, xs = _slice_ptr(x, "x")
+    gp, gs = _slice_ptr(grad, "grad")
+    op, os_ = _slice_ptr(out, "out")
+    _lib.call("vfi_resize_bilinear_backward", xp, xs, gp, gs, op, os_, n, c, h, w, grad.shape[2], grad.shape[3],
+              int(bool(relu_input)), _lib.stream_ptr(),
+              work=("byte", 4.0 * n * c * h * w * 6, "resize_bilinear_backward") if _lib.PROFILE is not None else None)
+    return out
+
+
 def _out_like(x, out, name):
     """`out`: None (a new tensor) or a contiguous tensor of x's shape the op writes into (a slice of a wider buffer: no
     concat copy afterwards)."""

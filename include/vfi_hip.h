@@ -279,6 +279,58 @@ int vfi_phasenet_emit_low(const float *pred, long long pred_bstride, const float
 int vfi_tanh_residual_clamp(const float *x, const float *base, float *y, long long count, vfi_stream_t stream);
 
 /* ------------------------------------------------------------------------------------
+ * Backward of FusionNet's layers (training, src/fusion_net/train.py + trainer.py:222-260): gradients of
+ * src/fusion_net/fusion_net.py:24-41 (convolutions) and :46-77 (forward).  Deterministic: no float atomics; every
+ * sum runs in a fixed order, so a call repeats its bits.
+ * ---------------------------------------------------------------------------------- */
+
+/* Minimum workspace (floats) of vfi_conv2d_backward_weight for a layer (-1 on bad arguments): one partial slab. */
+long long vfi_conv2d_backward_weight_workspace_floats(int Cout, int Cin, int KS);
+
+/* Weight (and bias) gradient of a vfi_conv2d layer, stride 1, KS in {1,3,5}, pad_mode zeros | reflect:
+ *   dw (Cout, Cin, KS, KS) plain OIHW: dw[co][ci][ky][kx] = sum_{n,y,x} dy[n,co,y,x] * xpad[n,ci,y+ky,x+kx]
+ *   dbias (Cout) = sum_{n,y,x} dy[n,co,y,x], or NULL (not produced)
+ * x (N, Cin, H, W) is the layer's input (the padding is resolved while loading, never materialised), dy (N, Cout, H, W)
+ * the gradient of its output; batch strides as for vfi_conv2d.  fp32 MFMA GEMM split over the pixels into S partial
+ * slabs of `workspace`, summed in slab order by a second pass.  S depends only on the shape and workspace_floats
+ * (at least vfi_conv2d_backward_weight_workspace_floats; about 1024 workgroups' worth is used when it fits). */
+int vfi_conv2d_backward_weight(const float *x, long long x_bstride, const float *dy, long long dy_bstride, float *dw,
+                               float *dbias, int N, int Cin, int H, int W, int Cout, int KS, int pad_mode, float *workspace,
+                               long long workspace_floats, vfi_stream_t stream);
+
+/* Minimum workspace (floats) of vfi_conv2d_backward_data (-1 on bad arguments): N*(Cin+Cout)*(H+2p)*(W+2p) for
+ * reflect padding p = (KS-1)/2 > 0, else 0. */
+long long vfi_conv2d_backward_data_workspace_floats(int N, int Cin, int H, int W, int Cout, int KS, int pad_mode);
+
+/* Input gradient of the same layer: dx (N, Cin, H, W) from dy (N, Cout, H, W).  packed_wt is vfi_conv2d_pack of the
+ * transposed, flipped weights W.transpose(0,1).flip(2,3) (Cout' = Cin, Cin' = Cout).  Zero padding (and KS = 1): one
+ * vfi_conv2d of dy with the same padding.  Reflect: dy zero-embedded into (H+2p) x (W+2p), vfi_conv2d with zero padding
+ * gives the gradient of the padded input, and each pad row / column is folded onto the interior pixel it mirrors
+ * (torch's reflection-pad backward).  Workspace beyond the minimum goes to vfi_conv2d's split-K. */
+int vfi_conv2d_backward_data(const float *dy, long long dy_bstride, const float *packed_wt, float *dx, long long dx_bstride,
+                             int N, int Cin, int H, int W, int Cout, int KS, int pad_mode, float *workspace,
+                             long long workspace_floats, vfi_stream_t stream);
+
+/* Backward of vfi_tanh_residual_clamp (fusion_net.py:70-77): m = [0 <= base + tanh x <= 1] (inclusive, as
+ * torch.clamp), grad_x = grad_y (1 - tanh^2 x) m, grad_base = grad_y m; either output may be NULL. */
+int vfi_tanh_residual_clamp_backward(const float *x, const float *base, const float *grad_y, float *grad_x,
+                                     float *grad_base, long long count, vfi_stream_t stream);
+
+/* Backward of FusionNet's encoder block glue (fusion_net.py:55-59): y = relu(conv) (N, C, H, W) feeds MaxPool2d(2) and
+ * the skip.  grad_y = ([first maximal element of each 2x2 window in row-major order] * grad_pooled + grad_skip) * [y > 0]
+ * (torch's max_pool2d routing).  grad_skip may be NULL.  H, W even. */
+int vfi_pool2_max_backward(const float *y, long long y_bstride, const float *grad_pooled, long long gp_bstride,
+                           const float *grad_skip, long long gs_bstride, float *grad_y, long long gy_bstride, int N, int C,
+                           int H, int W, vfi_stream_t stream);
+
+/* Adjoint of vfi_resize_bilinear with align_corners = 0 and Hout = 2 Hin, Wout = 2 Win (nn.Upsample(scale_factor=2) of
+ * fusion_net.py:42,65): grad_x (N, C, Hin, Win) gathered from grad_y (no atomics); relu_input multiplies by [x > 0]
+ * (x: the forward's source, may be NULL without relu_input).  The residual's gradient is grad_y itself. */
+int vfi_resize_bilinear_backward(const float *x, long long x_bstride, const float *grad_y, long long gy_bstride,
+                                 float *grad_x, long long gx_bstride, int N, int C, int Hin, int Win, int Hout, int Wout,
+                                 int relu_input, vfi_stream_t stream);
+
+/* ------------------------------------------------------------------------------------
  * Complex steerable pyramid (frequency domain), scale_factor-generalised
  * ---------------------------------------------------------------------------------- */
 
