@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: interpolated frames/s of the full fused per-frame path at 1920x1080.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \\
         bench.py --gpus N --steps K --warmup W
 
@@ -11,7 +11,10 @@ src/fusion_net/interpolate_twoframe.py:148-330 with output_baseline, as src/eval
 4 analyses and 5 syntheses, see vfi_pyr_apply_filter / _pair), PhaseNet, uncertainty maps incl. the 50x50 median,
 FusionNet) on synthetic frame pairs already resident in HBM.  Frames of a clip shard across ranks with no data-path
 collective (weak scaling: fixed work per GPU); weights are broadcast once from rank 0 over RCCL.
-Rank 0 prints ONE JSON line.
+Rank 0 prints ONE JSON line.  A plain run does only what that line's headline needs: set-up, the warm-up steps, the K timed
+steps, --dump-outputs if asked, the line.  --full adds the measurements that take time of their own after the timed
+steps: the per-kernel roofline of one frame alone (off with --no-profile), the CPU oracle on the same workload (off with
+--no-cpu-baseline; minutes), and the --repeats / --steps-720p legs.
 
 `python bench.py --gpus N` without a torchrun environment spawns its N ranks itself (a child
 `python -m torch.distributed.run ... bench.py`, started before this process has made any GPU call) and exits with
@@ -269,23 +272,31 @@ def main():
                     help="frames in flight per GPU (independent frames of the clip on separate HIP streams)")
     ap.add_argument("--graph", type=int, default=0,
                     help="1: capture each in-flight frame's ~700 launches into a hipGraph (torch.cuda.CUDAGraph) and replay it")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline run, also measure what takes time of its own: the per-kernel roofline (unless "
+                         "--no-profile), the CPU oracle baseline (unless --no-cpu-baseline), and --repeats / --steps-720p")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU oracle leg")
     ap.add_argument("--cpu-threads", type=int, default=0,
-                    help="threads of the CPU oracle leg (default: every core the process can use -- affinity mask cut to the cgroup quota)")
+                    help="threads of the CPU oracle leg of --full (default: every core the process can use -- affinity mask cut to "
+                         "the cgroup quota)")
     ap.add_argument("--repeats", type=int, default=1,
                     help="timed regions of --steps steps, back to back with the same barriers; `value` is the FIRST, all of them go to "
-                         "value_repeats (3: how far `value` moves from run to run)")
+                         "value_repeats (3: how far `value` moves from run to run); more than 1 needs --full")
     ap.add_argument("--cpu-baseline-runs", type=int, default=3,
-                    help="timed full-size runs of the CPU oracle (median reported); 3 = BASELINE.md's protocol, ~4 minutes")
+                    help="timed full-size runs of the CPU oracle leg of --full (median reported); 3 = BASELINE.md's protocol, "
+                         "~4 minutes")
     ap.add_argument("--steps-720p", type=int, default=0,
-                    help="extra timed steps at 1280x720 after the headline run (north_star asks for both sizes); 0 = skip")
-    ap.add_argument("--no-profile", action="store_true")
+                    help="with --full: extra timed steps at 1280x720 after the headline run (north_star asks for both sizes); "
+                         "0 = skip")
+    ap.add_argument("--no-profile", action="store_true", help="with --full: skip the per-kernel roofline")
     ap.add_argument("--dump-outputs", metavar="DIR",
                     help="after the timed steps, write what the last one returned (every array of rank 0's result dict) as "
                          "DIR/<name>.npy, float32, at most 64 MB in all (see dump_outputs)")
     args = ap.parse_args()
     if args.dump_outputs and args.steps < 1:
         ap.error("--dump-outputs needs --steps >= 1")
+    if not args.full and (args.repeats > 1 or args.steps_720p > 0):
+        ap.error("--repeats above 1 and --steps-720p are measurements beyond the headline: they need --full")
     if args.gpus > 1 and "RANK" not in os.environ and "WORLD_SIZE" not in os.environ:
         spawn_ranks(args.gpus)                               # never returns
 
@@ -417,7 +428,7 @@ def main():
         if value_720p is not None:
             line["value_720p"] = value_720p
             line["value_720p_note"] = f"same fused frame at 1280x720, {args.steps_720p} timed steps after the headline run, frames/s of all ranks"
-        if not args.no_profile:
+        if args.full and not args.no_profile:
             # Per-kernel algorithmic work / measured launch duration: HIP events on the launch stream around every library
             # call, over ONE frame running ALONE on the device on one stream after the timed region.  (With two frames in
             # flight the events of two streams overlap in time and would double-count, and a kernel's duration depends on
@@ -482,7 +493,7 @@ def main():
                                                "achieved": rate / div, "peak": peak, "unit": unit, "frac": rate / div / peak,
                                                "calls": v["calls"], "ms_per_frame": v["seconds"] * 1e3})
             line["stage_ms_isolated"] = {k: round(v["seconds"] * 1e3, 3) for k, v in sorted(agg.items(), key=lambda kv: -kv[1]["seconds"])[:14]}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline((h, w), runs=args.cpu_baseline_runs, threads=args.cpu_threads or None)
     if world > 1:
         dist.barrier()
