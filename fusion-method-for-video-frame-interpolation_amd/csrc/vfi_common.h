@@ -42,6 +42,8 @@ inline int current_device() {
 }
 
 __host__ __device__ inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
+// workgroups of 256 threads for a grid-stride loop over n elements (capped: the loop covers the rest)
+inline int blocks_1d(long long n) { long long b = (n + 255) / 256; return (int)(b > 16384 ? 16384 : (b < 1 ? 1 : b)); }
 
 }  // namespace vfi
 

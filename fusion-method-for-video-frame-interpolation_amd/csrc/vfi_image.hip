@@ -13,8 +13,8 @@
 
 namespace {
 
+using vfi::blocks_1d;
 using vfi::ceil_div;
-inline int blocks_1d(long long n) { long long b = (n + 255) / 256; return (int)(b > 16384 ? 16384 : (b < 1 ? 1 : b)); }
 
 // ---- colour -------------------------------------------------------------------------------------------
 // skimage.color.rgb2lab: sRGB -> linear -> XYZ (xyz_from_rgb) -> / D65 white -> f(t) -> Lab; then the

@@ -1,11 +1,6 @@
-// Complex steerable pyramid (frequency domain, scale_factor-generalised) for gfx950:
-// the arithmetic behind Pyramid.filter / inv_filter (reference call sites src/train/pyramid.py:35-46;
-// adapters coeff_to_values / values_to_coeff src/train/pyramid.py:48-112 are fused in).
-//
-// The reference delegates this arithmetic to the third-party `steerable.SCFpyr_PyTorch` (absent, fork
-// unknown: see DESIGN.md, "pyramid spec"); the spec implemented here is the one restated in
-// oracle/pyramid_cpu.py: level k works on the centred ceil(H/s^k) x ceil(W/s^k) window of the
-// spectrum, radial raised-cosine transition shifted by log2(s) per level, nbands oriented analytic bands.
+// Complex steerable pyramid (frequency domain, scale_factor-generalised) for gfx950: the kernels and the calls that run on
+// a plan.  The plan (spec, mask tables, transform tables, every level's resolved passes) is vfi_pyr_plan.hip; the calls
+// here read it through `const` pointers and write its workspace only.
 //
 // Roofline: HBM (target).  No FFT library is linked: the large levels run on the wave-private register FFT engine of
 // vfi_wfft.h (kernels in vfi_pyrw_kernels.h), every length that engine has no configuration for on the generic LDS
@@ -25,231 +20,17 @@
 //               (pyr_combine_kernel).
 //   backward  : vfi_pyr_synthesize_backward, the synthesis' adjoint = the analysis passes with the tables A_k (P_a with the
 //               synthesis' two-sided angle masks), the synthesis' 1/(H W), and a gradient epilogue on (phase, amplitude).
-// All mask tables are precomputed once per plan in double precision, stored in the unshifted (FFT-native)
-// index order so every table read is coalesced with the spectrum access.
-#include "vfi_common.h"
-#include "vfi_fft.h"
-#include "vfi_pyramid_wave.h"
+#include "vfi_pyr_plan.h"
 
-#include <cmath>
 #include <cstdlib>
-#include <map>
-#include <new>
 #include <type_traits>
 #include <vector>
 
 namespace {
 
+using vfi::blocks_1d;
 using vfi::ceil_div;
-constexpr int kMaxLevels = 40;
-constexpr int kMaxImages = 16;
-constexpr double kPi = 3.14159265358979323846;
-
-struct Level {
-    int h, w;          // window size
-    float *P_a;        // [nb][h][w] analysis  : lo0 * prod_{j<k} lomask_j * himask_k * angle mask (one sided), unshifted order
-    float *P_s;        // [nb][h][w] synthesis : angle mask (two sided) * himask
-    float *lomask;     // [h2][w2]  low-pass applied to the NEXT level's window, unshifted order of that window
-    float *A = nullptr;   // [nb][h][w] synthesis adjoint: lo0 * prod_{j<k} lomask_j * P_s (vfi_pyr_plan_prepare_adjoint)
-};
-
-}  // namespace
-
-struct vfi_pyr_plan {
-    int H, W, height, nbands, nlev, max_images;
-    double scale;
-    std::vector<Level> lev;      // nlev band levels
-    int hl, wl;                  // low residual size
-    float *lo0 = nullptr, *hi0 = nullptr;   // [H][W] unshifted
-    float *low_gain = nullptr;   // [hl][wl] lo0 * prod_j lomask_j on the low residual's window, unshifted
-    int tpitch_max = 0;          // row pitch of T the workspace is sized for (W rounded up to 16)
-    std::map<int, const float2 *> wave_tw[3];   // [pass kind] engine length -> stage twiddles (vfi_wfft.h)   // engine length -> stage twiddles (vfi_wfft.h)
-    // workspace (complex64 unless noted)
-    float2 *half0 = nullptr;     // N x H x (W/2+1)   R2C spectrum of the input / FFT of high on synthesis
-    float2 *half_hi = nullptr;   // N x H x (W/2+1)   high-pass half spectrum (C2R input)
-    float2 *bands = nullptr;     // N x nb x H x W    band spectra / coefficients of the current level
-    float2 *lod[2] = {nullptr, nullptr};   // N x H x W each: running low-pass spectrum (ping-pong)
-    std::map<int, vfi::fft::Plan1D> fft1d;   // transform length -> tables (vfi_fft.h)
-    unsigned *amp_bits = nullptr;            // kMaxLevels * 4 words: vfi_pyr_analyze_max
-    std::vector<void *> allocs;
-    // kept for vfi_pyr_plan_prepare_filter
-    std::vector<double> log_rad, xr0, yr, yir;
-    std::vector<float *> filters;   // [id] -> H x (W/2+1) radial gain tables
-    bool adjoint = false;           // Level::A built (vfi_pyr_plan_prepare_adjoint)
-};
-
-namespace {
-
-// ---- host-side mask construction (double precision, numpy semantics) -----------------------------------
-double interp(double x, const std::vector<double> &xp, const std::vector<double> &fp) {
-    const size_t n = xp.size();
-    if (x <= xp[0]) return fp[0];
-    if (x >= xp[n - 1]) return fp[n - 1];
-    size_t lo = 0, hi = n - 1;
-    while (hi - lo > 1) {
-        const size_t mid = (lo + hi) / 2;
-        if (xp[mid] <= x) lo = mid; else hi = mid;
-    }
-    const double slope = (fp[lo + 1] - fp[lo]) / (xp[lo + 1] - xp[lo]);
-    return slope * (x - xp[lo]) + fp[lo];
-}
-
-std::vector<double> linspace_grid(int m) {  // prepare_grid axis
-    std::vector<double> v(m);
-    const double start = -(double)(m / 2) / (m / 2.0);
-    const double stop = (double)(m / 2) / (m / 2.0) - (1 - m % 2) * 2.0 / m;
-    const double step = m > 1 ? (stop - start) / (m - 1) : 0.0;
-    for (int i = 0; i < m; ++i) v[i] = start + i * step;
-    if (m > 1) v[m - 1] = stop;
-    return v;
-}
-
-inline int level_size(int d, double s, int k) { return (int)std::ceil(d / std::pow(s, k) - 1e-9); }
-
-template <typename T>
-int dev_upload(vfi_pyr_plan *p, const std::vector<T> &host, T **dev) {
-    if (hipMalloc((void **)dev, host.size() * sizeof(T)) != hipSuccess) return VFI_ERR_NOMEM;
-    p->allocs.push_back(*dev);
-    if (hipMemcpy(*dev, host.data(), host.size() * sizeof(T), hipMemcpyHostToDevice) != hipSuccess) return VFI_ERR_LAUNCH;
-    return VFI_OK;
-}
-
-int dev_alloc(vfi_pyr_plan *p, void **dev, size_t bytes) {
-    if (hipMalloc(dev, bytes) != hipSuccess) return VFI_ERR_NOMEM;
-    p->allocs.push_back(*dev);
-    return VFI_OK;
-}
-
-// shifted-window index (DC at h/2) for an unshifted index u of a length-h axis
-inline int shifted_of(int u, int h) { return (u + h / 2) % h; }
-
-// upstream's angular LUTs: abscissae xc, one-sided analysis mask ya, two-sided synthesis mask ys
-void angle_luts(int nb, std::vector<double> &xc, std::vector<double> &ya, std::vector<double> &ys) {
-    const int lut = 1024, order = nb - 1;
-    const int nl = 3 * lut + 3;
-    xc.resize(nl); ya.resize(nl); ys.resize(nl);
-    double fact_o = 1, fact_2o = 1;
-    for (int i = 2; i <= order; ++i) fact_o *= i;
-    for (int i = 2; i <= 2 * order; ++i) fact_2o *= i;
-    const double cst = std::pow(2.0, 2 * order) * fact_o * fact_o / (nb * fact_2o);
-    for (int i = 0; i < nl; ++i) {
-        xc[i] = kPi * (double)(i - (2 * lut + 1)) / lut;
-        double alpha = std::fmod(xc[i] + kPi, 2 * kPi);
-        if (alpha < 0) alpha += 2 * kPi;
-        alpha -= kPi;
-        const double c = std::pow(std::cos(xc[i]), order);
-        ya[i] = 2.0 * std::sqrt(cst) * c * (std::fabs(alpha) < kPi / 2 ? 1.0 : 0.0);
-        ys[i] = std::sqrt(cst) * c;
-    }
-}
-
-// chain(spos, k) = lo0 * prod_{j<k} lomask_j at the full-grid (shifted) position spos: what the build's running low-pass
-// spectrum has been multiplied by when level k reads it (`lodft = dft * lo0mask`, then `lodft * lomask` per level)
-struct Chain {
-    const vfi_pyr_plan *p;
-    std::vector<std::vector<double>> xr_of;       // xr_of[j] = xr0 - j * log2(scale)
-    explicit Chain(const vfi_pyr_plan *pl) : p(pl), xr_of(pl->nlev + 1, pl->xr0) {
-        const double ls = std::log2(p->scale);
-        for (int j = 1; j <= p->nlev; ++j)
-            for (auto &x : xr_of[j]) x -= j * ls;
-    }
-    double operator()(size_t spos, int k) const {
-        double c = interp(p->log_rad[spos], xr_of[0], p->yir);
-        for (int j = 1; j <= k; ++j) c *= interp(p->log_rad[spos], xr_of[j], p->yir);
-        return c;
-    }
-};
-
-int build_tables(vfi_pyr_plan *p) {
-    const int H = p->H, W = p->W, nb = p->nbands;
-    const std::vector<double> gy = linspace_grid(H), gx = linspace_grid(W);
-    // log_rad / angle on the full shifted grid
-    std::vector<double> log_rad((size_t)H * W), angle((size_t)H * W);
-    for (int i = 0; i < H; ++i)
-        for (int j = 0; j < W; ++j) {
-            angle[(size_t)i * W + j] = std::atan2(gy[i], gx[j]);
-            log_rad[(size_t)i * W + j] = std::sqrt(gx[j] * gx[j] + gy[i] * gy[i]);
-        }
-    if (W > 1) log_rad[(size_t)(H / 2) * W + W / 2] = log_rad[(size_t)(H / 2) * W + W / 2 - 1];
-    for (auto &v : log_rad) v = std::log2(v);
-    // rcosFn(1, -0.5)
-    const int n = 256;
-    std::vector<double> xr(n + 3), yr(n + 3), yir(n + 3);
-    for (int i = 0; i < n + 3; ++i) {
-        const double x = kPi * (double)(i - n - 1) / 2.0 / n;
-        xr[i] = x;
-        yr[i] = std::cos(x) * std::cos(x);
-    }
-    yr[0] = yr[1];
-    yr[n + 2] = yr[n + 1];
-    for (int i = 0; i < n + 3; ++i) {
-        xr[i] = -0.5 + 2.0 / kPi * (xr[i] + kPi / 4.0);
-        yr[i] = std::sqrt(yr[i]);
-        yir[i] = std::sqrt(std::fabs(1.0 - yr[i] * yr[i]));
-    }
-    std::vector<double> xc, ya, ys;
-    angle_luts(nb, xc, ya, ys);
-    const int nl = (int)xc.size();
-    std::vector<double> xcb(nl);
-    p->log_rad = log_rad; p->xr0 = xr; p->yr = yr; p->yir = yir;
-
-    std::vector<float> t((size_t)H * W), t2((size_t)H * W);
-    for (int u = 0; u < H; ++u)
-        for (int v = 0; v < W; ++v) {
-            const size_t s = (size_t)shifted_of(u, H) * W + shifted_of(v, W);
-            t[(size_t)u * W + v] = (float)interp(log_rad[s], xr, yir);
-            t2[(size_t)u * W + v] = (float)interp(log_rad[s], xr, yr);
-        }
-    int rc;
-    if ((rc = dev_upload(p, t, &p->lo0)) || (rc = dev_upload(p, t2, &p->hi0))) return rc;
-
-    const double ls = std::log2(p->scale);
-    const Chain chain(p);
-    for (int k = 0; k < p->nlev; ++k) {
-        Level &L = p->lev[k];
-        for (auto &x : xr) x -= ls;
-        const int h = L.h, w = L.w, sy = H / 2 - h / 2, sx = W / 2 - w / 2;
-        std::vector<float> pa((size_t)nb * h * w), ps((size_t)nb * h * w);
-        std::vector<float> hm((size_t)h * w);
-        std::vector<double> ch((size_t)h * w);
-        for (int u = 0; u < h; ++u)
-            for (int v = 0; v < w; ++v) {
-                const size_t s = (size_t)(sy + shifted_of(u, h)) * W + (sx + shifted_of(v, w));
-                hm[(size_t)u * w + v] = (float)interp(log_rad[s], xr, yr);
-                ch[(size_t)u * w + v] = chain(s, k);
-            }
-        for (int b = 0; b < nb; ++b) {
-            for (int i = 0; i < nl; ++i) xcb[i] = xc[i] + kPi * b / nb;
-            for (int u = 0; u < h; ++u)
-                for (int v = 0; v < w; ++v) {
-                    const size_t s = (size_t)(sy + shifted_of(u, h)) * W + (sx + shifted_of(v, w));
-                    const size_t o = ((size_t)b * h + u) * w + v;
-                    // float32 tables of the oracle multiplied in fp32 there; here folded in double
-                    pa[o] = (float)((double)(float)interp(angle[s], xcb, ya) * (double)hm[(size_t)u * w + v] * ch[(size_t)u * w + v]);
-                    ps[o] = (float)((double)(float)interp(angle[s], xcb, ys) * (double)hm[(size_t)u * w + v]);
-                }
-        }
-        const int h2 = k + 1 < p->nlev ? p->lev[k + 1].h : p->hl, w2 = k + 1 < p->nlev ? p->lev[k + 1].w : p->wl;
-        const int sy2 = H / 2 - h2 / 2, sx2 = W / 2 - w2 / 2;
-        std::vector<float> lm((size_t)h2 * w2);
-        for (int u = 0; u < h2; ++u)
-            for (int v = 0; v < w2; ++v) {
-                const size_t s = (size_t)(sy2 + shifted_of(u, h2)) * W + (sx2 + shifted_of(v, w2));
-                lm[(size_t)u * w2 + v] = (float)interp(log_rad[s], xr, yir);
-            }
-        if ((rc = dev_upload(p, pa, &L.P_a)) || (rc = dev_upload(p, ps, &L.P_s)) || (rc = dev_upload(p, lm, &L.lomask)))
-            return rc;
-    }
-    {   // low residual: real(ifft2(window(dft) * lo0 * prod_j lomask_j))
-        const int h2 = p->hl, w2 = p->wl, sy2 = H / 2 - h2 / 2, sx2 = W / 2 - w2 / 2;
-        std::vector<float> lg((size_t)h2 * w2);
-        for (int u = 0; u < h2; ++u)
-            for (int v = 0; v < w2; ++v)
-                lg[(size_t)u * w2 + v] = (float)chain((size_t)(sy2 + shifted_of(u, h2)) * W + (sx2 + shifted_of(v, w2)), p->nlev);
-        if ((rc = dev_upload(p, lg, &p->low_gain))) return rc;
-    }
-    return VFI_OK;
-}
+using namespace vfi::pyr;
 
 // ---- device kernels ------------------------------------------------------------------------------------
 using vfi::pyrw::PlaneMap;      // where image d's band-0 plane goes (vfi_pyramid_wave.h)
@@ -812,88 +593,22 @@ __global__ __launch_bounds__(kThreads, kThreads / 128) void pyr_combine_cols_ker
     }
 }
 
-template <auto kernel>
-void allow_big_lds() {      // > 64 KiB of dynamic LDS needs the attribute, per KERNEL (not per signature) and device (idempotent)
-    static bool done[vfi::kMaxDevices] = {};
-    bool &d = done[vfi::current_device()];
+// Launches the smooth or the Bluestein instance of a generic-engine kernel.  > 64 KiB of dynamic LDS needs the attribute,
+// per KERNEL (not per signature) and device; it is set once (idempotent: racing threads store the same thing).
+template <auto bluestein, auto smooth, class Args>
+int launch_engine(bool blu, dim3 grid, size_t lds, hipStream_t s, const Args &a) {
+    static bool done[2][vfi::kMaxDevices] = {};
+    const auto kernel = blu ? bluestein : smooth;
+    bool &d = done[blu][vfi::current_device()];
     if (!d) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  (int)(vfi::fft::kLdsElemsMax * sizeof(float2) + 8192));
+        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                                 (int)(vfi::fft::kLdsElemsMax * sizeof(float2) + 8192));
+        if (e != hipSuccess) return vfi::fail(VFI_ERR_LAUNCH, "pyramid: set LDS size: %s", hipGetErrorString(e));
         d = true;
     }
-}
-
-// Column tile width and bands per transform call of a fused level kernel: large levels take the widest tile that fits
-// and one band per call; small levels (latency-bound: few workgroups, each a chain of short phases) put 2 or all 4 bands
-// through one call as extra lines, with tiles of >= 8 columns.
-void level_tiling(const vfi::fft::Plan1D &ph, int w, int *tile, int *bands) {
-    using namespace vfi::fft;
-    *tile = cols_per_group(ph, w);
-    *bands = 1;
-    for (int bp : {4, 2}) {
-        int c = *tile;
-        while (c > 8 && (bp * c * ph.m > max_elems(ph) || bp * c * col_pitch(ph, c) + ph.tw_len > kLdsElems)) c /= 2;
-        if (c >= 8 || c == *tile) {
-            if (bp * c * ph.m <= max_elems(ph) && bp * c * col_pitch(ph, c) + ph.tw_len <= kLdsElems) {
-                *tile = c;
-                *bands = bp;
-                return;
-            }
-        }
-    }
-}
-size_t level_lds_bytes(const vfi::fft::Plan1D &ph, int tile, int bands) {
-    return ((size_t)bands * tile * vfi::fft::col_pitch(ph, tile) + ph.tw_len) * sizeof(float2);
-}
-
-// ---- 2-D transforms = a row pass and a column pass of the LDS engine (vfi_fft.h / vfi_fft.hip) ---------------------------
-int get_fft(vfi_pyr_plan *p, int n, vfi::fft::Plan1D *out) {
-    auto it = p->fft1d.find(n);
-    if (it == p->fft1d.end()) {
-        vfi::fft::Plan1D pl;
-        const int rc = vfi::fft::make_plan(n, &pl, [](void *ctx, void *dev) { static_cast<vfi_pyr_plan *>(ctx)->allocs.push_back(dev); }, p);
-        if (rc) return rc;
-        it = p->fft1d.emplace(n, pl).first;
-    }
-    *out = it->second;
+    hipLaunchKernelGGL(kernel, grid, dim3(vfi::fft::kThreads), lds, s, a);
     return VFI_OK;
 }
-
-// ---- wave engine (vfi_wfft.h) selection: engine length of a pass or 0, and its stage twiddles (built once per plan) ----
-enum WavePass { kWaveRows = 0, kWaveAnaCols = 1, kWaveSynCols = 2 };
-int wave_twiddles(vfi_pyr_plan *p, WavePass kind, int M, const float2 **out) {
-    auto &cache = p->wave_tw[kind];
-    auto it = cache.find(M);
-    if (it == cache.end()) {
-        std::vector<float2> tw(4096);
-        const int cap = (int)tw.size();
-        const int cnt = kind == kWaveRows ? vfi::pyrw::rows_twiddles(M, tw.data(), cap)
-                                          : (kind == kWaveAnaCols ? vfi::pyrw::cols_twiddles(M, tw.data(), cap) : vfi::pyrw::syn_twiddles(M, tw.data(), cap));
-        if (cnt < 0) return vfi::fail(VFI_ERR_UNSUPPORTED, "pyramid: no wave-engine twiddles for length %d", M);
-        tw.resize(cnt > 0 ? cnt : 1);
-        float2 *dev = nullptr;
-        const int rc = dev_upload(p, tw, &dev);
-        if (rc) return rc;
-        it = cache.emplace(M, dev).first;
-    }
-    *out = it->second;
-    return VFI_OK;
-}
-// tables of a pass on the wave engine; tb->M == 0 when the engine has no configuration for this length
-int wave_tables(vfi_pyr_plan *p, WavePass kind, const vfi::fft::Plan1D &pl, vfi::pyrw::Tables *tb) {
-    // A/B switch: VFI_PYR_WAVE = bit mask of the passes that may run on the wave engine (1 rows, 2 analysis columns and
-    // plain column passes, 4 synthesis columns; default all, 0 = the generic LDS engine everywhere)
-    static const int allowed = [] { const char *e = getenv("VFI_PYR_WAVE"); return e ? atoi(e) : 7; }();
-    *tb = vfi::pyrw::Tables{};
-    const bool off = !((allowed >> (int)kind) & 1);
-    const int M = off ? 0 : (kind != kWaveRows ? vfi::pyrw::cols_engine_length(pl.n, pl.bluestein ? pl.m : 0) : vfi::pyrw::rows_engine_length(pl.n, pl.bluestein ? pl.m : 0));
-    if (!M) return VFI_OK;
-    const int rc = wave_twiddles(p, kind, M, &tb->tw);
-    if (rc) return rc;
-    tb->chirp = pl.chirp; tb->bfilt = pl.bfilt; tb->M = M; tb->n = pl.n; tb->bluestein = pl.bluestein;
-    return VFI_OK;
-}
-inline int round_up16(int x) { return (x + 15) & ~15; }
 
 // debugging aid (VFI_PYR_CHECK=1): wait for the stream and count the NaNs of a device array
 void debug_scan(const void *dev, size_t floats, hipStream_t s, const char *what, int level) {
@@ -908,62 +623,49 @@ void debug_scan(const void *dev, size_t floats, hipStream_t s, const char *what,
     if (bad) fprintf(stderr, "[vfi_pyr check] %s level %d: %zu NaNs of %zu floats, first at %zu\n", what, level, bad, floats, first);
 }
 
-// one row / column pass of a plain 2-D transform: on the wave engine where it has a configuration for the length,
-// otherwise on the generic LDS engine
-int pass_rows(vfi_pyr_plan *p, const vfi::fft::Plan1D &pw, const void *src, void *dst, long long rows, int src_pitch, int dst_pitch,
-              vfi::fft::RowLoad load, vfi::fft::RowStore store, bool inverse, hipStream_t s) {
+// ---- 2-D transforms = a row pass and a column pass, each on the wave engine where the plan resolved a configuration
+// for the length, otherwise on the generic LDS engine (vfi_fft.h / vfi_fft.hip) ------------------------------------------
+int pass_rows(const Size2D &z, const void *src, void *dst, long long rows, int src_pitch, int dst_pitch, vfi::fft::RowLoad load,
+              vfi::fft::RowStore store, bool inverse, hipStream_t s) {
     using namespace vfi::fft;
-    vfi::pyrw::Tables tb;
-    int rc = wave_tables(p, kWaveRows, pw, &tb);
-    if (rc) return rc;
+    const vfi::pyrw::Tables &tb = z.wave[kWaveRows];
     if (tb.M && rows < (1LL << 31)) {
         vfi::pyrw::GenRowsArgs a{tb, src, dst, (int)rows, src_pitch, dst_pitch, 1.0f};
         return vfi::pyrw::launch_gen_rows(a, (int)load, (int)store, inverse, s);      // (RowLoad / RowStore == GenRowKind values)
     }
-    RowArgs r{pw, src, dst, rows, src_pitch, dst_pitch, rows_per_group(pw, rows), 1.0f};
+    RowArgs r{z.pw, src, dst, rows, src_pitch, dst_pitch, rows_per_group(z.pw, rows), 1.0f};
     return launch_rows(r, load, store, inverse, s);
 }
-int pass_cols(vfi_pyr_plan *p, const vfi::fft::Plan1D &ph, float2 *data, int planes, int cols, int ld, bool inverse, hipStream_t s) {
+int pass_cols(const Size2D &z, float2 *data, int planes, int cols, int ld, bool inverse, hipStream_t s) {
     using namespace vfi::fft;
-    vfi::pyrw::Tables tb;
-    int rc = wave_tables(p, kWaveAnaCols, ph, &tb);      // (the plain column pass runs with the analysis column geometry)
-    if (rc) return rc;
+    const vfi::pyrw::Tables &tb = z.wave[kWaveAnaCols];      // (the plain column pass runs with the analysis column geometry)
     if (tb.M) {
         vfi::pyrw::GenColsArgs a{tb, data, planes, cols, ld, 1.0f};
         return vfi::pyrw::launch_gen_cols(a, inverse, s);
     }
-    ColArgs c{ph, data, planes, cols, ld, cols_per_group(ph, cols), 1.0f};
+    ColArgs c{z.ph, data, planes, cols, ld, cols_per_group(z.ph, cols), 1.0f};
     return launch_cols(c, inverse, s);
 }
 
-// in-place complex 2-D transform of `planes` dense h x w arrays (un-normalised)
-int fft2d_c2c(vfi_pyr_plan *p, float2 *data, int planes, int h, int w, bool inverse, hipStream_t s) {
-    using namespace vfi::fft;
-    Plan1D ph, pw;
-    int rc;
-    if ((rc = get_fft(p, h, &ph)) || (rc = get_fft(p, w, &pw))) return rc;
-    if ((rc = pass_cols(p, ph, data, planes, w, w, inverse, s))) return rc;
-    return pass_rows(p, pw, data, data, (long long)planes * h, w, w, kLoadComplex, kStoreComplex, inverse, s);
+// in-place complex 2-D transform of `planes` dense z.h x z.w arrays (un-normalised)
+int fft2d_c2c(const Size2D &z, float2 *data, int planes, bool inverse, hipStream_t s) {
+    const int rc = pass_cols(z, data, planes, z.w, z.w, inverse, s);
+    if (rc) return rc;
+    return pass_rows(z, data, data, (long long)planes * z.h, z.w, z.w, vfi::fft::kLoadComplex, vfi::fft::kStoreComplex, inverse, s);
 }
 // real H x W images -> half spectra N x H x (W/2+1)
-int fft2d_r2c(vfi_pyr_plan *p, const float *img, float2 *half, int N, hipStream_t s) {
-    using namespace vfi::fft;
-    Plan1D ph, pw;
-    int rc;
-    if ((rc = get_fft(p, p->H, &ph)) || (rc = get_fft(p, p->W, &pw))) return rc;
+int fft2d_r2c(const vfi_pyr_plan *p, const float *img, float2 *half, int N, hipStream_t s) {
     const int wh = p->W / 2 + 1;
-    if ((rc = pass_rows(p, pw, img, half, (long long)N * p->H, p->W, wh, kLoadReal, kStoreHalf, false, s))) return rc;
-    return pass_cols(p, ph, half, N, wh, wh, false, s);
+    const int rc = pass_rows(p->frame, img, half, (long long)N * p->H, p->W, wh, vfi::fft::kLoadReal, vfi::fft::kStoreHalf, false, s);
+    if (rc) return rc;
+    return pass_cols(p->frame, half, N, wh, wh, false, s);
 }
 // half spectra (destroyed) -> real images, un-normalised inverse
-int fft2d_c2r(vfi_pyr_plan *p, float2 *half, float *out, int N, hipStream_t s) {
-    using namespace vfi::fft;
-    Plan1D ph, pw;
-    int rc;
-    if ((rc = get_fft(p, p->H, &ph)) || (rc = get_fft(p, p->W, &pw))) return rc;
+int fft2d_c2r(const vfi_pyr_plan *p, float2 *half, float *out, int N, hipStream_t s) {
     const int wh = p->W / 2 + 1;
-    if ((rc = pass_cols(p, ph, half, N, wh, wh, true, s))) return rc;
-    return pass_rows(p, pw, half, out, (long long)N * p->H, wh, p->W, kLoadHalf, kStoreReal, true, s);
+    const int rc = pass_cols(p->frame, half, N, wh, wh, true, s);
+    if (rc) return rc;
+    return pass_rows(p->frame, half, out, (long long)N * p->H, wh, p->W, vfi::fft::kLoadHalf, vfi::fft::kStoreReal, true, s);
 }
 
 PlaneMap make_map(const int *plane_index, int level, int N, int nb, int flags) {
@@ -976,136 +678,221 @@ PlaneMap make_map(const int *plane_index, int level, int N, int nb, int flags) {
     return pm;
 }
 
-inline int blocks_1d(long long n) { long long b = (n + 255) / 256; return (int)(b > 16384 ? 16384 : (b < 1 ? 1 : b)); }
+// ---- the passes of one level: each takes the engine from the level's record and builds its arguments in one place ------
+// generic-engine geometry: column workgroups (tile_of_block deals them in whole groups of 8) and their LDS; rows per
+// workgroup of a level's row pass, its workgroups and LDS (the line bases follow the lines)
+inline int cols_blocks(const Level &L) { return 8 * ceil_div(ceil_div(L.w, L.tile), 8); }
+inline size_t cols_lds(const Level &L) {
+    return ((size_t)L.bands * L.tile * vfi::fft::col_pitch(L.ph, L.tile) + L.ph.tw_len) * sizeof(float2);
+}
+inline int level_row_lines(const Plan1D &pw, long long rows) {
+    const int lines = vfi::fft::rows_per_group(pw, rows);
+    return lines > 256 ? 256 : lines;
+}
+inline int rows_blocks(const RowsPolarArgs &ra) { return (int)((ra.rows + ra.lines - 1) / ra.lines); }
+inline size_t rows_lds(const RowsPolarArgs &ra) { return vfi::fft::row_lds_bytes(ra.pw, ra.lines, (size_t)ra.lines * sizeof(size_t)); }
+// the wave engine's form of a level's row pass (T with the pitch the plan resolved for that direction)
+vfi::pyrw::RowsArgs wave_rows_args(const Level &L, int tpitch, int planes, const RowsPolarArgs &g) {
+    return vfi::pyrw::RowsArgs{L.wave[kWaveRows], g.T, tpitch, g.phase, g.amp, g.pm, planes, L.h, L.w,
+                               g.inv_hw, g.phase_scale, g.amp_max, g.groups};
+}
 
-// generic-engine row pass of one level (analysis, or the synthesis adjoint with GRAD)
-template <bool GRAD>
-void launch_level_rows(const RowsArgsOf<GRAD> &ra, hipStream_t s) {
-    const dim3 grid((unsigned)((ra.rows + ra.lines - 1) / ra.lines));
-    const size_t lds = vfi::fft::row_lds_bytes(ra.pw, ra.lines, (size_t)ra.lines * sizeof(size_t));
-    if (ra.pw.bluestein) {
-        allow_big_lds<pyr_rows_polar_kernel<4, true, GRAD>>();
-        hipLaunchKernelGGL((pyr_rows_polar_kernel<4, true, GRAD>), grid, dim3(vfi::fft::kThreads), lds, s, ra);
-    } else {
-        allow_big_lds<pyr_rows_polar_kernel<4, false, GRAD>>();
-        hipLaunchKernelGGL((pyr_rows_polar_kernel<4, false, GRAD>), grid, dim3(vfi::fft::kThreads), lds, s, ra);
+// What vfi_pyr_analyze, vfi_pyr_analyze_max and vfi_pyr_synthesize_backward ask of the analysis passes.
+// adjoint: vfi_pyr_synthesize_backward runs them on the synthesis' adjoint: the level tables A_k in place of P_a, the
+// 1 / (H W) of the synthesis' final inverse in place of each level's 1 / (h w) (also on the low residual), and with
+// (phase, amplitude) the gradient epilogue of the row pass, which reads the forward's values
+struct AnalyzeCall {
+    float *high;
+    float *const *phase, *const *amp;
+    const int *plane_index;
+    float *low;
+    float phase_scale;
+    unsigned long long level_mask;
+    int flags;
+    float *amp_max = nullptr;      // vfi_pyr_analyze_max
+    int groups = 1;
+    float eps = 0.0f;
+    bool adjoint = false;
+    const float *const *fphase = nullptr, *const *famp = nullptr;   // forward inputs per level (unused with VFI_PYR_COMPLEX_COEFF)
+    bool grad() const { return adjoint && !(flags & VFI_PYR_COMPLEX_COEFF); }      // gradient epilogue on (phase, amplitude)
+};
+
+LevelColsArgs ana_cols_args(const vfi_pyr_plan *p, int k, const AnalyzeCall &c, float2 *T) {
+    const Level &L = p->lev[k];
+    return LevelColsArgs{L.ph, p->half0, T, c.adjoint ? L.A : L.P_a, L.h, L.w, p->H, p->W, L.tile, L.bands};
+}
+RowsPolarGradArgs ana_rows_args(const vfi_pyr_plan *p, int k, int N, const AnalyzeCall &c, float2 *T) {
+    const Level &L = p->lev[k];
+    const long long rows = (long long)N * p->nbands * L.h;
+    return RowsPolarGradArgs{{L.pw, T, c.phase[k], c.amp ? c.amp[k] : nullptr, make_map(c.plane_index, k, N, p->nbands, c.flags), rows, L.h,
+                              level_row_lines(L.pw, rows),
+                              c.adjoint ? 1.0f / ((float)p->H * (float)p->W) : 1.0f / ((float)L.h * (float)L.w), c.phase_scale,
+                              c.amp_max ? p->amp_bits + (size_t)k * c.groups : nullptr, c.groups},
+                             c.grad() ? c.fphase[k] : nullptr, c.grad() ? c.famp[k] : nullptr};
+}
+
+// ---- the small levels (<= 40 k coefficients per band: from 135 x 240 down at 1080p) as FOUR launches on the generic LDS
+// engine instead of two per level: column passes of the smooth / Bluestein heights, row passes of the smooth / Bluestein
+// widths; every level has its own region of T.  VFI_PYR_MULTI=0: one launch pair per level (A/B aid)
+unsigned long long multi_levels(const vfi_pyr_plan *p, int N, unsigned long long level_mask) {
+    static const bool multi_on = !(getenv("VFI_PYR_MULTI") && atoi(getenv("VFI_PYR_MULTI")) == 0);
+    // (coarsest first, while their T regions fit into the workspace together: it is sized for ONE level, the finest)
+    const size_t cap = (size_t)p->max_images * p->nbands * p->H * p->tpitch_max;
+    unsigned long long multi_mask = 0;
+    size_t need = 0;
+    int cnt = 0;
+    for (int k = p->nlev - 1; k >= 0 && cnt < kMaxMulti; --k) {
+        if (!((level_mask >> k) & 1ull)) continue;
+        const size_t t = (size_t)N * p->nbands * p->lev[k].h * p->lev[k].w;
+        if ((long long)p->lev[k].h * p->lev[k].w > 40000 || need + t > cap) break;
+        multi_mask |= 1ull << k; need += t; ++cnt;
     }
+    return multi_on && cnt >= 2 ? multi_mask : 0;
 }
 // the small levels' row passes in one launch; g holds the adjoint's form of every entry (sliced to the analysis form for !GRAD)
 template <bool GRAD>
-void launch_multi_rows(const MultiRowsT<RowsPolarGradArgs> &g, bool blu, size_t lds, hipStream_t s) {
+int launch_multi_rows(const MultiRowsT<RowsPolarGradArgs> &g, bool blu, size_t lds, hipStream_t s) {
     MultiRowsT<RowsArgsOf<GRAD>> m;
     m.count = g.count;
     for (int i = 0; i <= g.count; ++i) m.first[i] = g.first[i];
     for (int i = 0; i < g.count; ++i) m.lev[i] = g.lev[i];
-    const dim3 grid(m.first[m.count]);
-    if (blu) {
-        allow_big_lds<pyr_multi_rows_polar_kernel<4, true, GRAD>>();
-        hipLaunchKernelGGL((pyr_multi_rows_polar_kernel<4, true, GRAD>), grid, dim3(vfi::fft::kThreads), lds, s, m);
-    } else {
-        allow_big_lds<pyr_multi_rows_polar_kernel<4, false, GRAD>>();
-        hipLaunchKernelGGL((pyr_multi_rows_polar_kernel<4, false, GRAD>), grid, dim3(vfi::fft::kThreads), lds, s, m);
+    return launch_engine<pyr_multi_rows_polar_kernel<4, true, GRAD>, pyr_multi_rows_polar_kernel<4, false, GRAD>>(blu, dim3(m.first[m.count]), lds, s, m);
+}
+int analyze_multi(const vfi_pyr_plan *p, unsigned long long multi_mask, int N, const AnalyzeCall &c, hipStream_t s) {
+    MultiColsArgs mc[2];      // [bluestein]
+    MultiRowsT<RowsPolarGradArgs> mr[2];
+    size_t clds[2] = {0, 0}, rlds[2] = {0, 0};
+    for (int b = 0; b < 2; ++b) { mc[b].count = 0; mc[b].first[0] = 0; mr[b].count = 0; mr[b].first[0] = 0; }
+    float2 *T = p->bands;
+    for (int k = 0; k < p->nlev; ++k) {
+        if (!((multi_mask >> k) & 1ull)) continue;
+        const Level &L = p->lev[k];
+        MultiColsArgs &cm = mc[L.ph.bluestein ? 1 : 0];
+        cm.lev[cm.count] = ana_cols_args(p, k, c, T);
+        cm.first[cm.count + 1] = cm.first[cm.count] + cols_blocks(L);
+        ++cm.count;
+        clds[L.ph.bluestein ? 1 : 0] = std::max(clds[L.ph.bluestein ? 1 : 0], cols_lds(L));
+        MultiRowsT<RowsPolarGradArgs> &rm = mr[L.pw.bluestein ? 1 : 0];
+        const RowsPolarGradArgs &ra = rm.lev[rm.count] = ana_rows_args(p, k, N, c, T);
+        rm.first[rm.count + 1] = rm.first[rm.count] + rows_blocks(ra);
+        ++rm.count;
+        rlds[L.pw.bluestein ? 1 : 0] = std::max(rlds[L.pw.bluestein ? 1 : 0], rows_lds(ra));
+        T += (size_t)N * p->nbands * L.h * L.w;
     }
+    int rc = VFI_OK;
+    for (int b = 0; b < 2 && !rc; ++b)
+        if (mc[b].count)
+            rc = launch_engine<pyr_multi_level_cols_kernel<4, true>, pyr_multi_level_cols_kernel<4, false>>(b == 1, dim3(mc[b].first[mc[b].count], N),
+                                                                                                            clds[b], s, mc[b]);
+    for (int b = 0; b < 2 && !rc; ++b)
+        if (mr[b].count) rc = c.grad() ? launch_multi_rows<true>(mr[b], b == 1, rlds[b], s) : launch_multi_rows<false>(mr[b], b == 1, rlds[b], s);
+    return rc;
 }
 
-// vfi_pyr_synthesize_backward runs the analysis passes on the synthesis' adjoint: the level tables A_k in place of P_a, the
-// 1 / (H W) of the synthesis' final inverse in place of each level's 1 / (h w) (also on the low residual), and with
-// (phase, amplitude) the gradient epilogue of the row pass, which reads the forward's values
-struct Adjoint {
-    const float *const *phase, *const *amp;   // forward inputs per level (unused with VFI_PYR_COMPLEX_COEFF)
-};
+int ana_cols(const vfi_pyr_plan *p, int k, int N, const AnalyzeCall &c, hipStream_t s) {
+    const Level &L = p->lev[k];
+    const LevelColsArgs g = ana_cols_args(p, k, c, p->bands);
+    const vfi::pyrw::Tables &tb = L.wave[kWaveAnaCols];
+    if (!tb.M)
+        return launch_engine<pyr_level_cols_kernel<4, true>, pyr_level_cols_kernel<4, false>>(L.ph.bluestein, dim3(cols_blocks(L), N),
+                                                                                              cols_lds(L), s, g);
+    vfi::pyrw::AnaColsArgs ca{tb, g.src, p->W / 2 + 1, p->H, g.P, g.T, L.tpitch_ana, N, L.h, L.w};
+    const int rc = vfi::pyrw::launch_ana_cols(ca, s);
+    if (!rc) debug_scan(p->bands, (size_t)N * p->nbands * L.h * L.tpitch_ana * 2, s, "T after the wave column pass", k);
+    return rc;
+}
+
+// generic-engine row pass of one level (analysis, or the synthesis adjoint with GRAD)
+template <bool GRAD>
+int launch_level_rows(const RowsArgsOf<GRAD> &ra, hipStream_t s) {
+    return launch_engine<pyr_rows_polar_kernel<4, true, GRAD>, pyr_rows_polar_kernel<4, false, GRAD>>(ra.pw.bluestein, dim3(rows_blocks(ra)),
+                                                                                                      rows_lds(ra), s, ra);
+}
+int ana_rows(const vfi_pyr_plan *p, int k, int N, const AnalyzeCall &c, hipStream_t s) {
+    const Level &L = p->lev[k];
+    const RowsPolarGradArgs g = ana_rows_args(p, k, N, c, p->bands);
+    if (!L.wave[kWaveRows].M) return c.grad() ? launch_level_rows<true>(g, s) : launch_level_rows<false>(g, s);
+    const vfi::pyrw::RowsArgs ra = wave_rows_args(L, L.tpitch_ana, N * p->nbands, g);
+    return c.grad() ? vfi::pyrw::launch_rows_polar_grad(vfi::pyrw::RowsGradArgs{ra, g.fphase, g.famp}, s) : vfi::pyrw::launch_rows_polar(ra, s);
+}
+
+int pyr_analyze_impl(const vfi_pyr_plan *p, const float *img, int N, const AnalyzeCall &c, vfi_stream_t stream) {
+    VFI_REQUIRE(p && img, VFI_ERR_INVALID_ARG, "vfi_pyr_analyze: null pointer");
+    VFI_REQUIRE(!c.amp_max || (c.groups >= 1 && c.groups <= 4 && !(c.flags & VFI_PYR_COMPLEX_COEFF)), VFI_ERR_INVALID_ARG,
+                "vfi_pyr_analyze_max: groups must be 1..4 and the outputs (phase, amplitude)");
+    VFI_REQUIRE(N >= 1 && N <= p->max_images, VFI_ERR_INVALID_ARG, "vfi_pyr_analyze: N=%d (plan max %d)", N, p->max_images);
+    VFI_REQUIRE((c.phase && (c.amp || (c.flags & VFI_PYR_COMPLEX_COEFF))) || c.level_mask == 0, VFI_ERR_INVALID_ARG,
+                "vfi_pyr_analyze: null phase/amp tables");
+    for (int k = 0; k < p->nlev; ++k) {
+        if (!((c.level_mask >> k) & 1ull)) continue;
+        VFI_REQUIRE(c.phase[k] && ((c.flags & VFI_PYR_COMPLEX_COEFF) || c.amp[k]), VFI_ERR_INVALID_ARG,
+                    "vfi_pyr_analyze: null output for level %d", k);
+        VFI_REQUIRE(!c.grad() || (c.fphase[k] && c.famp[k]), VFI_ERR_INVALID_ARG, "vfi_pyr_synthesize_backward: null input for level %d", k);
+    }
+    hipStream_t s = vfi::as_stream(stream);
+    const int H = p->H, W = p->W;
+    const float inv_full = 1.0f / ((float)H * (float)W);
+    int rc;
+    if (c.amp_max && hipMemsetAsync(p->amp_bits, 0, sizeof(unsigned) * p->nlev * c.groups, s) != hipSuccess)
+        return vfi::fail(VFI_ERR_LAUNCH, "vfi_pyr_analyze_max: memset");
+    if ((rc = fft2d_r2c(p, img, p->half0, N, s))) return rc;
+    debug_scan(p->half0, (size_t)N * H * (W / 2 + 1) * 2, s, "half spectrum", -1);
+    const unsigned long long multi_mask = multi_levels(p, N, c.level_mask);
+    if (multi_mask && (rc = analyze_multi(p, multi_mask, N, c, s))) return rc;
+    for (int k = 0; k < p->nlev; ++k) {      // (the levels read the half spectrum directly: nothing to pass along)
+        if (!((c.level_mask >> k) & 1ull) || ((multi_mask >> k) & 1ull)) continue;
+        if ((rc = ana_cols(p, k, N, c, s)) || (rc = ana_rows(p, k, N, c, s))) return rc;
+    }
+    if (c.low) {  // low residual: real(ifft2(window(dft) * low_gain))
+        float2 *buf = p->lod[0];
+        const int tot1 = p->low.h * p->low.w;
+        hipLaunchKernelGGL(pyr_low_kernel, dim3(ceil_div(tot1, 256)), dim3(256), 0, s, p->half0, buf, p->low_gain, N, H, W, p->low.h, p->low.w);
+        if ((rc = fft2d_c2c(p->low, buf, N, true, s))) return rc;
+        const long long tot = (long long)N * tot1;
+        hipLaunchKernelGGL(complex_real_kernel, dim3(blocks_1d(tot)), dim3(256), 0, s, buf, c.low, tot,
+                           c.adjoint ? inv_full : 1.0f / ((float)p->low.h * (float)p->low.w));
+    }
+    if (c.high) {  // high residual: C2R of half * hi0 / (H W)
+        hipLaunchKernelGGL(pyr_high_kernel, dim3(ceil_div(W / 2 + 1, 256), H), dim3(256), 0, s, p->half0, p->half_hi, p->hi0, N, H, W, inv_full);
+        if ((rc = fft2d_c2r(p, p->half_hi, c.high, N, s))) return rc;
+    }
+    if (c.amp_max) {
+        const int count = p->nlev * c.groups;
+        hipLaunchKernelGGL(pyr_amp_max_finish_kernel, dim3(ceil_div(count, 64)), dim3(64), 0, s, p->amp_bits, c.amp_max, count, c.eps);
+    }
+    return vfi::check_launch("vfi_pyr_analyze");
+}
+
+// ---- synthesis passes of one level -------------------------------------------------------------------------------------
+// a level without bands only embeds the coarser spectrum res (h2 x w2) into cur
+void syn_embed(const vfi_pyr_plan *p, int k, int N, const float2 *res, int h2, int w2, float2 *cur, hipStream_t s) {
+    const Level &L = p->lev[k];
+    hipLaunchKernelGGL((pyr_combine_kernel<4>), dim3(ceil_div(L.w, 256), L.h), dim3(256), 0, s, p->bands, res, cur, L.P_s, L.lomask, N, L.h, L.w,
+                       h2, w2, 0);
+}
+int syn_rows(const vfi_pyr_plan *p, int k, int N, const float *phase, const float *amp, const PlaneMap &pm, hipStream_t s) {
+    const Level &L = p->lev[k];
+    const long long rows = (long long)N * p->nbands * L.h;
+    const RowsPolarArgs g{L.pw, p->bands, const_cast<float *>(phase), const_cast<float *>(amp), pm, rows, L.h, level_row_lines(L.pw, rows),
+                          1.0f, 1.0f, nullptr, 1};
+    if (L.wave[kWaveRows].M) return vfi::pyrw::launch_rows_from_polar(wave_rows_args(L, L.tpitch_syn, N * p->nbands, g), s);
+    return launch_engine<pyr_rows_from_polar_kernel<4, true>, pyr_rows_from_polar_kernel<4, false>>(L.pw.bluestein, dim3(rows_blocks(g)),
+                                                                                                    rows_lds(g), s, g);
+}
+// cur = this level's bands + the embedded coarser spectrum res (h2 x w2)
+int syn_cols(const vfi_pyr_plan *p, int k, int N, const float2 *res, int h2, int w2, float2 *cur, hipStream_t s) {
+    const Level &L = p->lev[k];
+    const vfi::pyrw::Tables &tb = L.wave[kWaveSynCols];
+    if (tb.M) {
+        vfi::pyrw::SynColsArgs ca{tb, p->bands, L.tpitch_syn, L.P_s, res, L.lomask, cur, N, L.h, L.w, h2, w2};
+        return vfi::pyrw::launch_syn_cols(ca, s);
+    }
+    const CombineColsArgs ca{L.ph, p->bands, res, cur, L.P_s, L.lomask, L.h, L.w, h2, w2, L.tile, L.bands};
+    return launch_engine<pyr_combine_cols_kernel<4, true>, pyr_combine_cols_kernel<4, false>>(L.ph.bluestein, dim3(cols_blocks(L), N),
+                                                                                              cols_lds(L), s, ca);
+}
 
 }  // namespace
-
-extern "C" int vfi_pyr_plan_create(int H, int W, int height, int nbands, double scale_factor, int max_images,
-                                   vfi_pyr_plan **out) {
-    VFI_REQUIRE(out, VFI_ERR_INVALID_ARG, "vfi_pyr_plan_create: null out");
-    *out = nullptr;
-    VFI_REQUIRE(H >= 4 && W >= 4 && height >= 3 && height - 2 <= kMaxLevels, VFI_ERR_INVALID_ARG,
-                "vfi_pyr_plan_create: bad size %dx%d height %d", H, W, height);
-    VFI_REQUIRE(nbands == 4, VFI_ERR_UNSUPPORTED, "vfi_pyr_plan_create: nbands=%d (the path uses 4)", nbands);
-    VFI_REQUIRE(scale_factor > 1.0 && scale_factor <= 2.0, VFI_ERR_INVALID_ARG, "vfi_pyr_plan_create: scale_factor %g", scale_factor);
-    VFI_REQUIRE(max_images >= 1 && max_images <= kMaxImages, VFI_ERR_INVALID_ARG, "vfi_pyr_plan_create: max_images %d", max_images);
-    vfi_pyr_plan *p = new (std::nothrow) vfi_pyr_plan();
-    VFI_REQUIRE(p, VFI_ERR_NOMEM, "vfi_pyr_plan_create: host allocation");
-    p->H = H; p->W = W; p->height = height; p->nbands = nbands; p->nlev = height - 2; p->scale = scale_factor;
-    p->max_images = max_images;
-    p->lev.resize(p->nlev);
-    for (int k = 0; k < p->nlev; ++k) { p->lev[k].h = level_size(H, scale_factor, k); p->lev[k].w = level_size(W, scale_factor, k); }
-    p->hl = level_size(H, scale_factor, p->nlev);
-    p->wl = level_size(W, scale_factor, p->nlev);
-    int rc = VFI_OK;
-    if (p->hl < 2 || p->wl < 2) rc = vfi::fail(VFI_ERR_SHAPE, "vfi_pyr_plan_create: height %d too large for %dx%d", height, H, W);
-    if (!rc) rc = build_tables(p);
-    {   // FFT tables of every length the plan can meet (so that no later call allocates)
-        vfi::fft::Plan1D tmp;
-        for (int k = 0; k <= p->nlev && !rc; ++k) {
-            vfi::pyrw::Tables tb;
-            rc = get_fft(p, k < p->nlev ? p->lev[k].h : p->hl, &tmp);
-            if (!rc && k < p->nlev) rc = wave_tables(p, kWaveAnaCols, tmp, &tb);
-            if (!rc && k < p->nlev) rc = wave_tables(p, kWaveSynCols, tmp, &tb);
-            if (!rc) rc = get_fft(p, k < p->nlev ? p->lev[k].w : p->wl, &tmp);
-            if (!rc && k < p->nlev) rc = wave_tables(p, kWaveRows, tmp, &tb);
-        }
-    }
-    p->tpitch_max = round_up16(W);
-    const size_t N = max_images, HW = (size_t)H * p->tpitch_max, half = (size_t)H * (W / 2 + 1);
-    if (!rc) rc = dev_alloc(p, (void **)&p->half0, N * half * sizeof(float2));
-    if (!rc) rc = dev_alloc(p, (void **)&p->half_hi, N * half * sizeof(float2));
-    if (!rc) rc = dev_alloc(p, (void **)&p->bands, N * nbands * HW * sizeof(float2));
-    if (!rc) rc = dev_alloc(p, (void **)&p->lod[0], N * HW * sizeof(float2));
-    if (!rc) rc = dev_alloc(p, (void **)&p->lod[1], N * HW * sizeof(float2));
-    if (!rc) rc = dev_alloc(p, (void **)&p->amp_bits, kMaxLevels * 4 * sizeof(unsigned));
-    if (!rc && getenv("VFI_PYR_POISON")) {      // debugging aid: NaN-fill the workspace, so a read of anything not yet written shows
-        (void)hipMemset(p->half0, 0xff, N * half * sizeof(float2));
-        (void)hipMemset(p->half_hi, 0xff, N * half * sizeof(float2));
-        (void)hipMemset(p->bands, 0xff, N * nbands * HW * sizeof(float2));
-        (void)hipMemset(p->lod[0], 0xff, N * HW * sizeof(float2));
-        (void)hipMemset(p->lod[1], 0xff, N * HW * sizeof(float2));
-    }
-    if (rc) {
-        if (rc == VFI_ERR_NOMEM) vfi::set_error("vfi_pyr_plan_create: device allocation failed");
-        vfi_pyr_plan_destroy(p);
-        return rc;
-    }
-    *out = p;
-    return VFI_OK;
-}
-
-extern "C" int vfi_pyr_plan_prepare_filter(vfi_pyr_plan *p, unsigned long long level_mask, int keep_high, int keep_low,
-                                           int *filter_id) {
-    VFI_REQUIRE(p && filter_id, VFI_ERR_INVALID_ARG, "vfi_pyr_plan_prepare_filter: null pointer");
-    const int H = p->H, W = p->W, wh = W / 2 + 1;
-    const double ls = std::log2(p->scale);
-    std::vector<float> g((size_t)H * wh);
-    for (int u = 0; u < H; ++u)
-        for (int v = 0; v < wh; ++v) {
-            const int fy = u <= H - H / 2 - 1 ? u : u - H, fx = v;          // signed frequencies (v < wh: non-negative)
-            const double lr = p->log_rad[(size_t)shifted_of(u, H) * W + shifted_of(v, W)];
-            const double lo0 = interp(lr, p->xr0, p->yir), hi0 = interp(lr, p->xr0, p->yr);
-            double lowchain = 1.0, acc = 0.0;       // prod_{j<k} lomask_j^2 on the running window
-            std::vector<double> xr = p->xr0;
-            for (int k = 0; k <= p->nlev; ++k) {
-                const int h = k < p->nlev ? p->lev[k].h : p->hl, w = k < p->nlev ? p->lev[k].w : p->wl;
-                const bool inside = fy >= -(h / 2) && fy <= h - h / 2 - 1 && fx >= -(w / 2) && fx <= w - w / 2 - 1;
-                if (!inside) { lowchain = 0.0; break; }
-                if (k == p->nlev) break;
-                for (auto &x : xr) x -= ls;
-                const double hm = interp(lr, xr, p->yr), lm = interp(lr, xr, p->yir);
-                if ((level_mask >> k) & 1ull) acc += lowchain * hm * hm;
-                lowchain *= lm * lm;
-            }
-            if (keep_low) acc += lowchain;
-            const double gain = (keep_high ? hi0 * hi0 : 0.0) + lo0 * lo0 * acc;
-            g[(size_t)u * wh + v] = (float)(gain / ((double)H * W));
-        }
-    float *dev = nullptr;
-    int rc = dev_upload(p, g, &dev);
-    if (rc) return vfi::fail(rc, "vfi_pyr_plan_prepare_filter: device allocation / upload failed");
-    p->filters.push_back(dev);
-    *filter_id = (int)p->filters.size() - 1;
-    return VFI_OK;
-}
 
 extern "C" int vfi_pyr_apply_filter(vfi_pyr_plan *p, int filter_id, const float *img, int N, float *out, vfi_stream_t stream) {
     VFI_REQUIRE(p && img && out, VFI_ERR_INVALID_ARG, "vfi_pyr_apply_filter: null pointer");
@@ -1138,183 +925,10 @@ extern "C" int vfi_pyr_apply_filter_pair(vfi_pyr_plan *p, int filter_a, const fl
     return vfi::check_launch("vfi_pyr_apply_filter_pair");
 }
 
-extern "C" int vfi_pyr_plan_destroy(vfi_pyr_plan *p) {
-    if (!p) return VFI_OK;
-    for (void *d : p->allocs) (void)hipFree(d);
-    delete p;
-    return VFI_OK;
-}
-
-extern "C" int vfi_pyr_plan_level_size(const vfi_pyr_plan *p, int level, int *h, int *w) {
-    VFI_REQUIRE(p && h && w, VFI_ERR_INVALID_ARG, "vfi_pyr_plan_level_size: null pointer");
-    VFI_REQUIRE(level >= 0 && level <= p->nlev, VFI_ERR_INVALID_ARG, "vfi_pyr_plan_level_size: level %d", level);
-    *h = level < p->nlev ? p->lev[level].h : p->hl;
-    *w = level < p->nlev ? p->lev[level].w : p->wl;
-    return VFI_OK;
-}
-
-static int pyr_analyze_impl(vfi_pyr_plan *p, const float *img, int N, float *high, float *const *phase,
-                            float *const *amp, const int *plane_index, float *low, float phase_scale,
-                            unsigned long long level_mask, int flags, float *amp_max, int groups, float eps, vfi_stream_t stream,
-                            const Adjoint *adj = nullptr) {
-    VFI_REQUIRE(p && img, VFI_ERR_INVALID_ARG, "vfi_pyr_analyze: null pointer");
-    VFI_REQUIRE(!amp_max || (groups >= 1 && groups <= 4 && !(flags & VFI_PYR_COMPLEX_COEFF)), VFI_ERR_INVALID_ARG,
-                "vfi_pyr_analyze_max: groups must be 1..4 and the outputs (phase, amplitude)");
-    VFI_REQUIRE(N >= 1 && N <= p->max_images, VFI_ERR_INVALID_ARG, "vfi_pyr_analyze: N=%d (plan max %d)", N, p->max_images);
-    VFI_REQUIRE((phase && (amp || (flags & VFI_PYR_COMPLEX_COEFF))) || level_mask == 0, VFI_ERR_INVALID_ARG,
-                "vfi_pyr_analyze: null phase/amp tables");
-    hipStream_t s = vfi::as_stream(stream);
-    const int H = p->H, W = p->W, nb = p->nbands;
-    const bool grad = adj && !(flags & VFI_PYR_COMPLEX_COEFF);      // gradient epilogue on (phase, amplitude)
-    const float inv_full = 1.0f / ((float)H * (float)W);
-    int rc;
-    if (amp_max && hipMemsetAsync(p->amp_bits, 0, sizeof(unsigned) * p->nlev * groups, s) != hipSuccess)
-        return vfi::fail(VFI_ERR_LAUNCH, "vfi_pyr_analyze_max: memset");
-    if ((rc = fft2d_r2c(p, img, p->half0, N, s))) return rc;
-    debug_scan(p->half0, (size_t)N * H * (W / 2 + 1) * 2, s, "half spectrum", -1);
-    // ---- the small levels (<= 40 k coefficients per band: from 135 x 240 down at 1080p) as FOUR launches on the generic LDS
-    // engine instead of two per level: column passes of the smooth / Bluestein heights, row passes of the smooth / Bluestein
-    // widths; every level has its own region of T.  VFI_PYR_MULTI=0: one launch pair per level (A/B aid)
-    unsigned long long multi_mask = 0;
-    {
-        static const bool multi_on = !(getenv("VFI_PYR_MULTI") && atoi(getenv("VFI_PYR_MULTI")) == 0);
-        // (coarsest first, while their T regions fit into the workspace together: it is sized for ONE level, the finest)
-        const size_t cap = (size_t)p->max_images * nb * H * p->tpitch_max;
-        size_t need = 0;
-        int cnt = 0;
-        for (int k = p->nlev - 1; k >= 0 && cnt < kMaxMulti; --k) {
-            if (!((level_mask >> k) & 1ull)) continue;
-            const size_t t = (size_t)N * nb * p->lev[k].h * p->lev[k].w;
-            if ((long long)p->lev[k].h * p->lev[k].w > 40000 || need + t > cap) break;
-            multi_mask |= 1ull << k; need += t; ++cnt;
-        }
-        if (!multi_on || cnt < 2) multi_mask = 0;
-    }
-    if (multi_mask) {
-        using namespace vfi::fft;
-        MultiColsArgs mc[2];      // [bluestein]
-        MultiRowsT<RowsPolarGradArgs> mr[2];
-        size_t clds[2] = {0, 0}, rlds[2] = {0, 0};
-        for (int b = 0; b < 2; ++b) { mc[b].count = 0; mc[b].first[0] = 0; mr[b].count = 0; mr[b].first[0] = 0; }
-        size_t toff = 0;          // (float2 elements into p->bands)
-        for (int k = 0; k < p->nlev; ++k) {
-            if (!((multi_mask >> k) & 1ull)) continue;
-            const Level &L = p->lev[k];
-            VFI_REQUIRE(phase[k] && ((flags & VFI_PYR_COMPLEX_COEFF) || amp[k]), VFI_ERR_INVALID_ARG,
-                        "vfi_pyr_analyze: null output for level %d", k);
-            VFI_REQUIRE(!grad || (adj->phase[k] && adj->amp[k]), VFI_ERR_INVALID_ARG, "vfi_pyr_synthesize_backward: null input for level %d", k);
-            Plan1D ph, pw;
-            if ((rc = get_fft(p, L.h, &ph)) || (rc = get_fft(p, L.w, &pw))) return rc;
-            float2 *T = p->bands + toff;
-            toff += (size_t)N * nb * L.h * L.w;
-            int tile, bpp;
-            level_tiling(ph, L.w, &tile, &bpp);
-            MultiColsArgs &c = mc[ph.bluestein ? 1 : 0];
-            c.lev[c.count] = LevelColsArgs{ph, p->half0, T, adj ? L.A : L.P_a, L.h, L.w, H, W, tile, bpp};
-            c.first[c.count + 1] = c.first[c.count] + 8 * ceil_div(ceil_div(L.w, tile), 8);
-            ++c.count;
-            clds[ph.bluestein ? 1 : 0] = std::max(clds[ph.bluestein ? 1 : 0], level_lds_bytes(ph, tile, bpp));
-            const long long rows = (long long)N * nb * L.h;
-            int lines = rows_per_group(pw, rows);
-            if (lines > 256) lines = 256;
-            MultiRowsT<RowsPolarGradArgs> &r = mr[pw.bluestein ? 1 : 0];
-            r.lev[r.count] = RowsPolarGradArgs{{pw, T, phase[k], amp ? amp[k] : nullptr, make_map(plane_index, k, N, nb, flags), rows, L.h, lines,
-                                                adj ? inv_full : 1.0f / ((float)L.h * (float)L.w), phase_scale,
-                                                amp_max ? p->amp_bits + (size_t)k * groups : nullptr, groups},
-                                               grad ? adj->phase[k] : nullptr, grad ? adj->amp[k] : nullptr};
-            r.first[r.count + 1] = r.first[r.count] + (int)((rows + lines - 1) / lines);
-            ++r.count;
-            rlds[pw.bluestein ? 1 : 0] = std::max(rlds[pw.bluestein ? 1 : 0], row_lds_bytes(pw, lines, (size_t)lines * sizeof(size_t)));
-        }
-        if (mc[0].count) {
-            allow_big_lds<pyr_multi_level_cols_kernel<4, false>>();
-            hipLaunchKernelGGL((pyr_multi_level_cols_kernel<4, false>), dim3(mc[0].first[mc[0].count], N), dim3(kThreads), clds[0], s, mc[0]);
-        }
-        if (mc[1].count) {
-            allow_big_lds<pyr_multi_level_cols_kernel<4, true>>();
-            hipLaunchKernelGGL((pyr_multi_level_cols_kernel<4, true>), dim3(mc[1].first[mc[1].count], N), dim3(kThreads), clds[1], s, mc[1]);
-        }
-        for (int b = 0; b < 2; ++b)
-            if (mr[b].count) {
-                if (grad) launch_multi_rows<true>(mr[b], b == 1, rlds[b], s);
-                else launch_multi_rows<false>(mr[b], b == 1, rlds[b], s);
-            }
-    }
-    for (int k = 0; k < p->nlev; ++k) {
-        const Level &L = p->lev[k];
-        if (!((level_mask >> k) & 1ull) || ((multi_mask >> k) & 1ull)) continue;      // (the levels read the half spectrum directly: nothing to pass along)
-        VFI_REQUIRE(phase[k] && ((flags & VFI_PYR_COMPLEX_COEFF) || amp[k]), VFI_ERR_INVALID_ARG,
-                    "vfi_pyr_analyze: null output for level %d", k);
-        VFI_REQUIRE(!grad || (adj->phase[k] && adj->amp[k]), VFI_ERR_INVALID_ARG, "vfi_pyr_synthesize_backward: null input for level %d", k);
-        using namespace vfi::fft;
-        const float *Q = adj ? L.A : L.P_a;
-        const float row_scale = adj ? inv_full : 1.0f / ((float)L.h * (float)L.w);
-        Plan1D ph, pw;
-        vfi::pyrw::Tables tbh, tbw;
-        if ((rc = get_fft(p, L.h, &ph)) || (rc = get_fft(p, L.w, &pw)) || (rc = wave_tables(p, kWaveAnaCols, ph, &tbh)) ||
-            (rc = wave_tables(p, kWaveRows, pw, &tbw)))
-            return rc;
-        const int tpitch = tbh.M && tbw.M ? round_up16(L.w) : L.w;      // (the generic kernels address T densely)
-        const PlaneMap pm = make_map(plane_index, k, N, nb, flags);
-        unsigned *amax = amp_max ? p->amp_bits + (size_t)k * groups : nullptr;
-        if (tbh.M) {
-            vfi::pyrw::AnaColsArgs ca{tbh, p->half0, W / 2 + 1, H, Q, p->bands, tpitch, N, L.h, L.w};
-            if ((rc = vfi::pyrw::launch_ana_cols(ca, s))) return rc;
-            debug_scan(p->bands, (size_t)N * nb * L.h * tpitch * 2, s, "T after the wave column pass", k);
-        } else {
-            int tile, bpp;
-            level_tiling(ph, L.w, &tile, &bpp);
-            LevelColsArgs ca{ph, p->half0, p->bands, Q, L.h, L.w, H, W, tile, bpp};
-            const dim3 cgrid(8 * ceil_div(ceil_div(L.w, ca.tile), 8), N);
-            const size_t clds = level_lds_bytes(ph, tile, bpp);
-            if (ph.bluestein) {
-                allow_big_lds<pyr_level_cols_kernel<4, true>>();
-                hipLaunchKernelGGL((pyr_level_cols_kernel<4, true>), cgrid, dim3(kThreads), clds, s, ca);
-            } else {
-                allow_big_lds<pyr_level_cols_kernel<4, false>>();
-                hipLaunchKernelGGL((pyr_level_cols_kernel<4, false>), cgrid, dim3(kThreads), clds, s, ca);
-            }
-        }
-        if (tbw.M) {
-            vfi::pyrw::RowsArgs ra{tbw, p->bands, tpitch, phase[k], amp ? amp[k] : nullptr, pm, N * nb, L.h, L.w,
-                                   row_scale, phase_scale, amax, groups};
-            if (grad) rc = vfi::pyrw::launch_rows_polar_grad(vfi::pyrw::RowsGradArgs{ra, adj->phase[k], adj->amp[k]}, s);
-            else rc = vfi::pyrw::launch_rows_polar(ra, s);
-            if (rc) return rc;
-        } else {
-            const long long rows = (long long)N * nb * L.h;
-            int lines = rows_per_group(pw, rows);
-            if (lines > 256) lines = 256;
-            RowsPolarArgs ra{pw, p->bands, phase[k], amp ? amp[k] : nullptr, pm, rows, L.h, lines, row_scale, phase_scale, amax, groups};
-            if (grad) launch_level_rows<true>(RowsPolarGradArgs{ra, adj->phase[k], adj->amp[k]}, s);
-            else launch_level_rows<false>(ra, s);
-        }
-    }
-    if (low) {  // low residual: real(ifft2(window(dft) * low_gain))
-        float2 *buf = p->lod[0];
-        const int tot1 = p->hl * p->wl;
-        hipLaunchKernelGGL(pyr_low_kernel, dim3(ceil_div(tot1, 256)), dim3(256), 0, s, p->half0, buf, p->low_gain, N, H, W, p->hl, p->wl);
-        if ((rc = fft2d_c2c(p, buf, N, p->hl, p->wl, true, s))) return rc;
-        const long long tot = (long long)N * tot1;
-        hipLaunchKernelGGL(complex_real_kernel, dim3(blocks_1d(tot)), dim3(256), 0, s, buf, low, tot,
-                           adj ? inv_full : 1.0f / ((float)p->hl * (float)p->wl));
-    }
-    if (high) {  // high residual: C2R of half * hi0 / (H W)
-        hipLaunchKernelGGL(pyr_high_kernel, dim3(ceil_div(W / 2 + 1, 256), H), dim3(256), 0, s, p->half0, p->half_hi, p->hi0, N, H, W,
-                           1.0f / ((float)H * (float)W));
-        if ((rc = fft2d_c2r(p, p->half_hi, high, N, s))) return rc;
-    }
-    if (amp_max) {
-        const int count = p->nlev * groups;
-        hipLaunchKernelGGL(pyr_amp_max_finish_kernel, dim3(ceil_div(count, 64)), dim3(64), 0, s, p->amp_bits, amp_max, count, eps);
-    }
-    return vfi::check_launch("vfi_pyr_analyze");
-}
-
 extern "C" int vfi_pyr_analyze(vfi_pyr_plan *p, const float *img, int N, float *high, float *const *phase,
                                float *const *amp, const int *plane_index, float *low, float phase_scale,
                                unsigned long long level_mask, int flags, vfi_stream_t stream) {
-    return pyr_analyze_impl(p, img, N, high, phase, amp, plane_index, low, phase_scale, level_mask, flags, nullptr, 1, 0.0f, stream);
+    return pyr_analyze_impl(p, img, N, AnalyzeCall{high, phase, amp, plane_index, low, phase_scale, level_mask, flags}, stream);
 }
 
 extern "C" int vfi_pyr_analyze_max(vfi_pyr_plan *p, const float *img, int N, float *high, float *const *phase,
@@ -1322,7 +936,9 @@ extern "C" int vfi_pyr_analyze_max(vfi_pyr_plan *p, const float *img, int N, flo
                                    unsigned long long level_mask, int flags, float *amp_max, int groups, float eps,
                                    vfi_stream_t stream) {
     VFI_REQUIRE(amp_max, VFI_ERR_INVALID_ARG, "vfi_pyr_analyze_max: null amp_max");
-    return pyr_analyze_impl(p, img, N, high, phase, amp, plane_index, low, phase_scale, level_mask, flags, amp_max, groups, eps, stream);
+    AnalyzeCall c{high, phase, amp, plane_index, low, phase_scale, level_mask, flags};
+    c.amp_max = amp_max; c.groups = groups; c.eps = eps;
+    return pyr_analyze_impl(p, img, N, c, stream);
 }
 
 extern "C" int vfi_pyr_synthesize(vfi_pyr_plan *p, const float *high, const float *const *phase, const float *const *amp,
@@ -1333,72 +949,26 @@ extern "C" int vfi_pyr_synthesize(vfi_pyr_plan *p, const float *high, const floa
     VFI_REQUIRE((phase && (amp || (flags & VFI_PYR_COMPLEX_COEFF))) || level_mask == 0, VFI_ERR_INVALID_ARG,
                 "vfi_pyr_synthesize: null phase/amp tables");
     hipStream_t s = vfi::as_stream(stream);
-    const int H = p->H, W = p->W, nb = p->nbands;
+    const int H = p->H, W = p->W;
     int rc;
     // coarsest: res = FFT(low) (zeros when low is NULL)
     float2 *res = p->lod[p->nlev & 1];
     {
-        const long long tot = (long long)N * p->hl * p->wl;
+        const long long tot = (long long)N * p->low.h * p->low.w;
         hipLaunchKernelGGL(real_to_complex_kernel, dim3(blocks_1d(tot)), dim3(256), 0, s, low, res, tot);
-        if (low && (rc = fft2d_c2c(p, res, N, p->hl, p->wl, false, s))) return rc;
+        if (low && (rc = fft2d_c2c(p->low, res, N, false, s))) return rc;
     }
     for (int k = p->nlev - 1; k >= 0; --k) {
-        const Level &L = p->lev[k];
-        const int h2 = k + 1 < p->nlev ? p->lev[k + 1].h : p->hl, w2 = k + 1 < p->nlev ? p->lev[k + 1].w : p->wl;
-        const int hb = (level_mask >> k) & 1ull ? 1 : 0;
+        const Size2D &next = k + 1 < p->nlev ? p->lev[k + 1] : p->low;
         float2 *cur = p->lod[k & 1];
-        if (!hb) {      // no bands at this level: embed the coarser spectrum only
-            hipLaunchKernelGGL((pyr_combine_kernel<4>), dim3(ceil_div(L.w, 256), L.h), dim3(256), 0, s, p->bands, res, cur, L.P_s,
-                               L.lomask, N, L.h, L.w, h2, w2, 0);
-            res = cur;
-            continue;
-        }
-        VFI_REQUIRE(phase[k] && ((flags & VFI_PYR_COMPLEX_COEFF) || amp[k]), VFI_ERR_INVALID_ARG,
-                    "vfi_pyr_synthesize: null input for level %d", k);
-        using namespace vfi::fft;
-        Plan1D ph, pw;
-        vfi::pyrw::Tables tbh, tbw;
-        if ((rc = get_fft(p, L.h, &ph)) || (rc = get_fft(p, L.w, &pw)) || (rc = wave_tables(p, kWaveSynCols, ph, &tbh)) ||
-            (rc = wave_tables(p, kWaveRows, pw, &tbw)))
-            return rc;
-        const int tpitch = tbh.M && tbw.M ? round_up16(L.w) : L.w;
-        const PlaneMap pm = make_map(plane_index, k, N, nb, flags);
-        if (tbw.M) {
-            vfi::pyrw::RowsArgs ra{tbw, p->bands, tpitch, const_cast<float *>(phase[k]), amp ? const_cast<float *>(amp[k]) : nullptr, pm,
-                                   N * nb, L.h, L.w, 1.0f, 1.0f, nullptr, 1};
-            if ((rc = vfi::pyrw::launch_rows_from_polar(ra, s))) return rc;
+        if (!((level_mask >> k) & 1ull)) {
+            syn_embed(p, k, N, res, next.h, next.w, cur, s);
         } else {
-            const long long rows = (long long)N * nb * L.h;
-            int lines = rows_per_group(pw, rows);
-            if (lines > 256) lines = 256;
-            RowsPolarArgs ra{pw, p->bands, const_cast<float *>(phase[k]), amp ? const_cast<float *>(amp[k]) : nullptr, pm, rows, L.h,
-                             lines, 1.0f, 1.0f, nullptr, 1};
-            if (pw.bluestein) {
-                allow_big_lds<pyr_rows_from_polar_kernel<4, true>>();
-                hipLaunchKernelGGL((pyr_rows_from_polar_kernel<4, true>), dim3((unsigned)((rows + lines - 1) / lines)), dim3(kThreads),
-                                   row_lds_bytes(pw, lines, (size_t)lines * sizeof(size_t)), s, ra);
-            } else {
-                allow_big_lds<pyr_rows_from_polar_kernel<4, false>>();
-                hipLaunchKernelGGL((pyr_rows_from_polar_kernel<4, false>), dim3((unsigned)((rows + lines - 1) / lines)), dim3(kThreads),
-                                   row_lds_bytes(pw, lines, (size_t)lines * sizeof(size_t)), s, ra);
-            }
-        }
-        if (tbh.M) {
-            vfi::pyrw::SynColsArgs ca{tbh, p->bands, tpitch, L.P_s, res, L.lomask, cur, N, L.h, L.w, h2, w2};
-            if ((rc = vfi::pyrw::launch_syn_cols(ca, s))) return rc;
-        } else {
-            int tile, bpp;
-            level_tiling(ph, L.w, &tile, &bpp);
-            CombineColsArgs ca{ph, p->bands, res, cur, L.P_s, L.lomask, L.h, L.w, h2, w2, tile, bpp};
-            if (ph.bluestein) {
-                allow_big_lds<pyr_combine_cols_kernel<4, true>>();
-                hipLaunchKernelGGL((pyr_combine_cols_kernel<4, true>), dim3(8 * ceil_div(ceil_div(L.w, ca.tile), 8), N), dim3(kThreads),
-                                   level_lds_bytes(ph, tile, bpp), s, ca);
-            } else {
-                allow_big_lds<pyr_combine_cols_kernel<4, false>>();
-                hipLaunchKernelGGL((pyr_combine_cols_kernel<4, false>), dim3(8 * ceil_div(ceil_div(L.w, ca.tile), 8), N), dim3(kThreads),
-                                   level_lds_bytes(ph, tile, bpp), s, ca);
-            }
+            VFI_REQUIRE(phase[k] && ((flags & VFI_PYR_COMPLEX_COEFF) || amp[k]), VFI_ERR_INVALID_ARG,
+                        "vfi_pyr_synthesize: null input for level %d", k);
+            if ((rc = syn_rows(p, k, N, phase[k], amp ? amp[k] : nullptr, make_map(plane_index, k, N, p->nbands, flags), s)) ||
+                (rc = syn_cols(p, k, N, res, next.h, next.w, cur, s)))
+                return rc;
         }
         res = cur;
     }
@@ -1408,54 +978,10 @@ extern "C" int vfi_pyr_synthesize(vfi_pyr_plan *p, const float *high, const floa
         hi_half = p->half0;
     }
     hipLaunchKernelGGL(pyr_final_kernel, dim3(ceil_div(W, 256), H), dim3(256), 0, s, res, hi_half, p->lo0, p->hi0, N, H, W);
-    if ((rc = fft2d_c2c(p, res, N, H, W, true, s))) return rc;
+    if ((rc = fft2d_c2c(p->frame, res, N, true, s))) return rc;
     const long long tot = (long long)N * H * W;
     hipLaunchKernelGGL(complex_real_kernel, dim3(blocks_1d(tot)), dim3(256), 0, s, res, img, tot, 1.0f / ((float)H * (float)W));
     return vfi::check_launch("vfi_pyr_synthesize");
-}
-
-// A_k[b] = lo0 * prod_{j<k} lomask_j * himask_k * two-sided angle mask b on level k's window (unshifted order): P_a with the
-// synthesis' angle masks.  The synthesis is real-linear in the band coefficients z_{k,b}; its adjoint applied to a gradient
-// image g is  grad z_{k,b} = 1/(H W) * IFFT2_k,unnormalised( i * window_k(FFT2(g)) * A_k[b] )  -- an analysis level with
-// these tables and the synthesis' final 1/(H W) (conj of the forward's -i is +i, the analysis' rotation).
-extern "C" int vfi_pyr_plan_prepare_adjoint(vfi_pyr_plan *p) {
-    VFI_REQUIRE(p, VFI_ERR_INVALID_ARG, "vfi_pyr_plan_prepare_adjoint: null plan");
-    if (p->adjoint) return VFI_OK;
-    const int H = p->H, W = p->W, nb = p->nbands;
-    const std::vector<double> gy = linspace_grid(H), gx = linspace_grid(W);
-    std::vector<double> xc, ya, ys;
-    angle_luts(nb, xc, ya, ys);
-    std::vector<double> xcb(xc.size()), xr = p->xr0;
-    const double ls = std::log2(p->scale);
-    const Chain chain(p);
-    std::vector<std::vector<float>> tabs(p->nlev);
-    for (int k = 0; k < p->nlev; ++k) {
-        const Level &L = p->lev[k];
-        for (auto &x : xr) x -= ls;
-        const int h = L.h, w = L.w, sy = H / 2 - h / 2, sx = W / 2 - w / 2;
-        std::vector<double> g((size_t)h * w);      // himask_k * chain, as build_tables folds P_a
-        for (int u = 0; u < h; ++u)
-            for (int v = 0; v < w; ++v) {
-                const size_t s = (size_t)(sy + shifted_of(u, h)) * W + (sx + shifted_of(v, w));
-                g[(size_t)u * w + v] = (double)(float)interp(p->log_rad[s], xr, p->yr) * chain(s, k);
-            }
-        std::vector<float> &a = tabs[k];
-        a.resize((size_t)nb * h * w);
-        for (int b = 0; b < nb; ++b) {
-            for (size_t i = 0; i < xc.size(); ++i) xcb[i] = xc[i] + kPi * b / nb;
-            for (int u = 0; u < h; ++u)
-                for (int v = 0; v < w; ++v) {
-                    const int i = sy + shifted_of(u, h), j = sx + shifted_of(v, w);
-                    a[((size_t)b * h + u) * w + v] = (float)((double)(float)interp(std::atan2(gy[i], gx[j]), xcb, ys) * g[(size_t)u * w + v]);
-                }
-        }
-    }
-    for (int k = 0; k < p->nlev; ++k) {
-        const int rc = dev_upload(p, tabs[k], &p->lev[k].A);
-        if (rc) return vfi::fail(rc, "vfi_pyr_plan_prepare_adjoint: device allocation / upload failed");
-    }
-    p->adjoint = true;
-    return VFI_OK;
 }
 
 extern "C" int vfi_pyr_synthesize_backward(vfi_pyr_plan *p, const float *grad_img, int N, const float *const *phase,
@@ -1466,7 +992,7 @@ extern "C" int vfi_pyr_synthesize_backward(vfi_pyr_plan *p, const float *grad_im
     VFI_REQUIRE(p->adjoint, VFI_ERR_INVALID_ARG, "vfi_pyr_synthesize_backward: call vfi_pyr_plan_prepare_adjoint first");
     VFI_REQUIRE((flags & VFI_PYR_COMPLEX_COEFF) || level_mask == 0 || (phase && amp), VFI_ERR_INVALID_ARG,
                 "vfi_pyr_synthesize_backward: null forward phase/amp tables");
-    const Adjoint adj{phase, amp};
-    return pyr_analyze_impl(p, grad_img, N, grad_high, grad_phase, grad_amp, plane_index, grad_low, 1.0f, level_mask, flags,
-                            nullptr, 1, 0.0f, stream, &adj);
+    AnalyzeCall c{grad_high, grad_phase, grad_amp, plane_index, grad_low, 1.0f, level_mask, flags};
+    c.adjoint = true; c.fphase = phase; c.famp = amp;
+    return pyr_analyze_impl(p, grad_img, N, c, stream);
 }
