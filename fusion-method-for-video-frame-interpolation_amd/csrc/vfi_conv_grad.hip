@@ -331,6 +331,11 @@ extern "C" long long vfi_conv2d_backward_weight_workspace_floats(int Cout, int C
     return (long long)Cout * (Cin * KS * KS + 1);
 }
 
+extern "C" int vfi_conv2d_backward_weight_splits(int N, int Cin, int H, int W, int Cout, int KS, long long workspace_floats) {
+    if (N <= 0 || Cin <= 0 || Cout <= 0 || H <= 0 || W <= 0 || (KS != 1 && KS != 3 && KS != 5)) return -1;
+    return wgrad_plan(N, Cin, H, W, Cout, KS, workspace_floats).splits;
+}
+
 extern "C" int vfi_conv2d_backward_weight(const float *x, long long x_bstride, const float *dy, long long dy_bstride,
                                           float *dw, float *dbias, int N, int Cin, int H, int W, int Cout, int KS,
                                           int pad_mode, float *workspace, long long workspace_floats, vfi_stream_t stream) {

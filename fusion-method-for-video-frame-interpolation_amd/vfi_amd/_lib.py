@@ -75,7 +75,20 @@ SIGNATURES = {
     "vfi_tanh_residual_clamp_backward": [c_f] * 5 + [c_l, c_s],
     "vfi_pool2_max_backward": [c_f, c_l] * 4 + [c_i] * 4 + [c_s],
     "vfi_resize_bilinear_backward": [c_f, c_l] * 3 + [c_i] * 7 + [c_s],
+    "vfi_conv2d_backward_weight_splits": [c_i] * 6 + [c_l],
+    "vfi_add": [c_f, c_l] * 3 + [c_i, c_l, c_s],
+    "vfi_relu_mask": [c_f, c_l] * 4 + [c_i, c_l, c_s],
+    "vfi_sigmoid_backward": [c_f, c_f, c_f, c_l, c_s],
+    "vfi_replicate_pad": [c_f, c_l, c_f] + [c_i] * 5 + [c_s],
+    "vfi_pool2_avg_backward": [c_f, c_l] * 4 + [c_i] * 4 + [c_s],
+    "vfi_upsample2x_backward": [c_f, c_l] * 3 + [c_i] * 4 + [c_s],
+    "vfi_adacof_smooth_forward": [c_f] * 10 + [c_i] * 4 + [c_fl, c_s],
+    "vfi_adacof_blend_backward": [c_f] * 8 + [c_i] * 6 + [c_fl, c_s],
+    "vfi_adacof_head_backward": [c_f] * 8 + [c_l] + [c_f] * 4 + [c_i] * 4 + [c_fl, c_s],
+    "vfi_charbonnier_forward": [c_f, c_f, c_l, c_fl, c_f, c_f, c_s],
+    "vfi_charbonnier_backward": [c_f] * 5 + [c_l, c_fl, c_s],
 }
+REDUCE_WORKSPACE_FLOATS = 4096      # VFI_REDUCE_WORKSPACE_FLOATS
 # entry points that return a value instead of a vfi_status
 RESTYPES = {"vfi_conv2d_packed_floats": c_l, "vfi_conv2d_backward_weight_workspace_floats": c_l,
             "vfi_conv2d_backward_data_workspace_floats": c_l}

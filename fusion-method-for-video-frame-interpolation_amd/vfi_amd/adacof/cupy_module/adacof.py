@@ -47,28 +47,33 @@ class FunctionAdaCoF(torch.autograd.Function):
         both offset gradients on offset_i).  A non-contiguous ``grad_output`` (e.g. from ``out.sum()``) is made
         contiguous instead of asserted on (adacof.py:380)."""
         input, weight, offset_i, offset_j = ctx.saved_tensors
-        dilation = ctx.dilation
-        n, c, hin, win = input.shape
-        f = int(math.sqrt(weight.size(1)))
-        h, w = weight.size(2), weight.size(3)
-        grad_output = grad_output.contiguous()
         need = ctx.needs_input_grad
-        new = lambda: torch.empty((n, f * f, h, w), dtype=input.dtype, device=input.device)
         grad_input = torch.zeros_like(input) if need[0] else None
-        grad_weight = new() if need[1] else None
-        grad_offset_i = new() if need[2] else None
-        grad_offset_j = new() if need[3] else None
-        n_out = sum(g is not None for g in (grad_weight, grad_offset_i, grad_offset_j))
-        if n_out:
-            want_off = grad_offset_i is not None or grad_offset_j is not None
-            d = _lib.dptr
-            _lib.call("vfi_adacof_backward", d(grad_output, "grad_output"), d(input, "input"),
-                      d(weight, "weight") if want_off else None, d(offset_i, "offset_i"), d(offset_j, "offset_j"),
-                      d(grad_weight), d(grad_offset_i), d(grad_offset_j), n, c, hin, win, h, w, f, int(dilation),
-                      _lib.stream_ptr(),
-                      work=("byte", float(n) * h * w * (4 * c + 4 * f * f * (2 + want_off + n_out)),
-                            "adacof_backward_kernel"))
-        return grad_input, grad_weight, grad_offset_i, grad_offset_j, None
+        return (grad_input, *adacof_backward(grad_output.contiguous(), input, weight, offset_i, offset_j, ctx.dilation,
+                                             need[1:4]), None)
+
+
+def adacof_backward(grad_output, input, weight, offset_i, offset_j, dilation, need=(True, True, True)):
+    """(grad_weight, grad_offset_i, grad_offset_j) of the sampling, each None unless `need` asks: one vfi_adacof_backward
+    launch.  `input` is the padded planar frame the forward sampled."""
+    n, c, hin, win = input.shape
+    f = int(math.sqrt(weight.size(1)))
+    h, w = weight.size(2), weight.size(3)
+    new = lambda: torch.empty((n, f * f, h, w), dtype=input.dtype, device=input.device)
+    grad_weight = new() if need[0] else None
+    grad_offset_i = new() if need[1] else None
+    grad_offset_j = new() if need[2] else None
+    n_out = sum(g is not None for g in (grad_weight, grad_offset_i, grad_offset_j))
+    if n_out:
+        want_off = grad_offset_i is not None or grad_offset_j is not None
+        d = _lib.dptr
+        _lib.call("vfi_adacof_backward", d(grad_output, "grad_output"), d(input, "input"),
+                  d(weight, "weight") if want_off else None, d(offset_i, "offset_i"), d(offset_j, "offset_j"),
+                  d(grad_weight), d(grad_offset_i), d(grad_offset_j), n, c, hin, win, h, w, f, int(dilation),
+                  _lib.stream_ptr(),
+                  work=("byte", float(n) * h * w * (4 * c + 4 * f * f * (2 + want_off + n_out)),
+                        "adacof_backward_kernel"))
+    return grad_weight, grad_offset_i, grad_offset_j
 
 
 def adacof_fused(frame0, frame2, w1, a1, b1, w2, a2, b2, occ, dilation,

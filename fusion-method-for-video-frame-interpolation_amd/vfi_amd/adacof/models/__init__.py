@@ -26,6 +26,5 @@ class Model(nn.Module):
         return self.model.get_kernel(frame0, frame1)
 
     def train(self, mode=True):
-        if mode:
-            raise NotImplementedError("vfi_amd implements the inference path only (eval mode)")
-        return super().train(False)
+        """Allowed when the wrapped model allows it (the plain variant; the fusion variant raises NotImplementedError)."""
+        return super().train(mode)

@@ -95,7 +95,11 @@ class KernelEstimation(PackedModule):
         return ops.conv2d(x, pc, "zeros", "relu", residual=skip, upsample2x=True)
 
     def forward_x6(self, x6, softmax=True):
-        """softmax=False returns the Subnet_weight LOGITS (the sampler folds the softmax in)."""
+        """softmax=False returns the Subnet_weight LOGITS (the sampler folds the softmax in).  In training mode with grad
+        mode on and a parameter requiring grad, the same layers run as one autograd node whose backward is HIP
+        (softmaxed weights only); otherwise the inference sequence below runs."""
+        if softmax and self.wants_graph():
+            return _KernelEstimationFunction.apply(self, x6, *self.parameters())
         p = self.packed()
         c1, q1 = self._basic_pooled(p["moduleConv1"], x6)          # (c1 itself is not a skip connection; q = AvgPool2d(c))
         c2, q2 = self._basic_pooled(p["moduleConv2"], q1)
@@ -132,6 +136,180 @@ class KernelEstimation(PackedModule):
     def forward(self, rfield0, rfield2):
         """Reference signature (fusion_adacofnet.py:109): two mean-subtracted (N,3,H,W) frames."""
         return self.forward_x6(torch.cat([rfield0, rfield2], 1).contiguous())
+
+    # ---- training (DESIGN.md section 13) ----------------------------------------------------------------------------
+    def train(self, mode=True):
+        """No BatchNorm, no dropout: the mode changes no arithmetic.  Training mode only lets forward / forward_x6 record
+        the autograd graph (one node, HIP backward) when a parameter requires grad."""
+        return torch.nn.Module.train(self, mode)
+
+    def wants_graph(self):
+        """FusionNet.forward's rule: grad mode on, module training, a parameter requiring grad."""
+        return torch.is_grad_enabled() and self.training and any(t.requires_grad for t in self.parameters())
+
+    def live_convs(self):
+        """(name, ConvParams) of the 59 convolutions in state-dict order (all of them run)."""
+        return [(k, m) for k, m in self.named_modules() if isinstance(m, ConvParams)]
+
+    def packed_transposed(self):
+        """W.transpose(0,1).flip(2,3) packs for the input gradients, keyed by module name (`heads0`: the 448 -> 64 pack of
+        the seven heads' shared first convolution), cached beside the forward packs as FusionNet.packed_transposed does.
+        The first layer's is never needed."""
+        p = self.packed()
+        if "T" not in p:
+            with torch.no_grad():
+                t = {k: ops.packed_transposed(m.weight) for k, m in self.live_convs()
+                     if k != "moduleConv1.0" and not (k.endswith(".0") and k.split(".")[0] in HEADS)}
+                t["heads0"] = ops.packed_transposed(torch.cat([getattr(self, h)[0].weight for h in HEADS], 0))
+                p["T"] = t
+            dev = next(self.parameters()).device
+            if dev.type == "cuda":
+                torch.cuda.current_stream(dev).synchronize()
+        return p["T"]
+
+    def forward_train(self, x6, keep):
+        """The layers of forward_x6 with everything the backward needs kept in `keep`: every ReLU output, the block
+        inputs, the upsampled inputs of the upsample -> conv pairs, and relu(conv(up(x))) apart from the skip it is added
+        to (the ReLU's mask cannot be recovered from the sum).  -> (W1 logits, A1, B1, W2 logits, A2, B2, sigmoid Occ)."""
+        p = self.packed()
+
+        def block(name, x, pooled):
+            acts = [x]
+            for pc in p[name][:-1]:
+                acts.append(ops.conv2d(acts[-1], pc, "zeros", "relu"))
+            if pooled:
+                y, q = ops.conv2d_pool2(acts[-1], p[name][-1], False, "zeros", "relu")
+                return acts + [y], q
+            return acts + [ops.conv2d(acts[-1], p[name][-1], "zeros", "relu")], None
+
+        enc, x = {}, x6
+        for i in range(1, 6):
+            enc[i], x = block(f"moduleConv{i}", x, True)
+        dec, up = {}, {}
+        for i in (5, 4, 3, 2):
+            dec[i], _ = block(f"moduleDeconv{i}", x, False)
+            d = dec[i][-1]
+            u = ops.resize_bilinear(d, (2 * d.shape[2], 2 * d.shape[3]), align_corners=True)
+            r = ops.conv2d(u, p[f"moduleUpsample{i}"], "zeros", "relu")
+            up[i] = (u, r)
+            x = ops.add(r, enc[i][-1])
+        h0 = ops.conv2d(x, p["heads0"], "zeros", "relu")            # (N, 448, h, w)
+        heads, outs = {}, []
+        for i, name in enumerate(HEADS):
+            c_mid, c_up, c_out = p[name]
+            m = ops.conv2d(h0[:, 64 * i:64 * (i + 1)], c_mid, "zeros", "relu")
+            t = ops.conv2d(m, c_up, "zeros", "relu")
+            u = ops.resize_bilinear(t, (2 * t.shape[2], 2 * t.shape[3]), align_corners=True)
+            heads[name] = (m, t, u)
+            # the occlusion tail as upsample -> 64 -> 1 conv (the tap-sum form is an inference-only rewrite)
+            outs.append(ops.conv2d(u, c_out, "zeros", "sigmoid" if name == "moduleOcclusion" else None))
+        keep.update(enc=enc, dec=dec, up=up, x_heads=x, h0=h0, heads=heads)
+        return tuple(outs)
+
+    def backward_train(self, keep, g_outs, need):
+        """HIP backward of forward_train.  g_outs: gradients of the seven head convolutions' outputs (for Occlusion: of
+        the pre-sigmoid map); need: {parameter name: bool}.  -> {parameter name: gradient}.  Gradients are produced only
+        where asked; the walk stops at the last layer that something below still needs, and the first layer's input
+        gradient is never computed."""
+        pT = self.packed_transposed()
+        convs = dict(self.live_convs())
+        grads = {}
+        want = lambda k: need.get(k + ".weight", False) or need.get(k + ".bias", False)
+        head_keys = {h: [f"{h}.{i}" for i in (0, 2, 4, 7)] for h in HEADS}
+        trunk = any(want(k) for k in convs if k.split(".")[0] not in HEADS)
+
+        def layer(k, x, dy, want_dx, out=None):
+            if want(k):
+                dw, db = ops.conv2d_backward_weight(x, dy, 3, "zeros", bias=need.get(k + ".bias", False))
+                grads[k + ".weight"], grads[k + ".bias"] = dw, db
+            return ops.conv2d_backward_data(dy, pT[k], "zeros", out=out) if want_dx else None
+
+        x, h0 = keep["x_heads"], keep["h0"]
+        active = [h for h in HEADS if trunk or any(want(k) for k in head_keys[h])]
+        g448 = ops.new(tuple(h0.shape), h0) if active else None
+        for name in active:
+            i = HEADS.index(name)
+            sl = slice(64 * i, 64 * (i + 1))
+            m, t, u = keep["heads"][name]
+            below = trunk or want(f"{name}.0")
+            deeper = lambda k: below or any(want(q) for q in head_keys[name][:head_keys[name].index(k)])
+            g = layer(f"{name}.7", u, g_outs[i].contiguous(), deeper(f"{name}.7"))
+            if g is None:
+                continue
+            g = ops.upsample2x_backward(g, mask_src=t)
+            g = layer(f"{name}.4", m, g, deeper(f"{name}.4"))
+            if g is None:
+                continue
+            ops.relu_mask_(g, m)
+            layer(f"{name}.2", h0[:, sl], g, below, out=g448[:, sl] if below else None)
+            if below:
+                ops.relu_mask_(g448[:, sl], h0[:, sl])
+        if len(active) == len(HEADS) and all(want(f"{h}.0") for h in HEADS):
+            # the shared first convolution stays one 64 -> 448 bank: one weight-gradient call, split over the parameters
+            dw, db = ops.conv2d_backward_weight(x, g448, 3, "zeros", bias=True)
+            for i, h in enumerate(HEADS):
+                grads[f"{h}.0.weight"], grads[f"{h}.0.bias"] = dw[64 * i:64 * (i + 1)], db[64 * i:64 * (i + 1)]
+        else:
+            for h in active:
+                if want(f"{h}.0"):
+                    i = HEADS.index(h)
+                    layer(f"{h}.0", x, g448[:, 64 * i:64 * (i + 1)], False)
+        if not trunk:
+            return grads
+        g = ops.conv2d_backward_data(g448, pT["heads0"], "zeros")   # 448 -> 64: sums the seven heads' contributions
+
+        def block_backward(name, acts, g, want_dx):
+            """g: gradient of the block's last pre-activation (already masked) -> gradient of the block's input."""
+            g = layer(f"{name}.4", acts[2], g, True)
+            ops.relu_mask_(g, acts[2])
+            g = layer(f"{name}.2", acts[1], g, True)
+            ops.relu_mask_(g, acts[1])
+            return layer(f"{name}.0", acts[0], g, want_dx)
+
+        g_skip = {}
+        for i in (2, 3, 4, 5):              # decoder, in reverse: x_i = relu(conv(up(d_i))) + c_i
+            u, r = keep["up"][i]
+            g_skip[i] = g                   # the skip's gradient is the sum's own
+            gr = ops.relu_mask_(g, r, out=ops.new(tuple(g.shape), g))
+            gu = layer(f"moduleUpsample{i}.1", u, gr, True)
+            acts = keep["dec"][i]
+            g = block_backward(f"moduleDeconv{i}", acts, ops.upsample2x_backward(gu, mask_src=acts[3]), True)
+        for i in (5, 4, 3, 2, 1):           # encoder: c_i feeds AvgPool2d(2) and (i >= 2) the skip
+            acts = keep["enc"][i]
+            gc = ops.pool2_avg_backward(acts[3], g, g_skip.get(i))
+            g = block_backward(f"moduleConv{i}", acts, gc, i > 1)
+        return grads
+
+
+class _KernelEstimationFunction(torch.autograd.Function):
+    """KernelEstimation.forward_x6 as one autograd node: (net, x6, *parameters) -> the seven maps.  The backward turns
+    the maps' gradients into those of the head convolutions' outputs (softmax backward through vfi_adacof_head_backward
+    without smoothness terms, vfi_sigmoid_backward) and walks KernelEstimation.backward_train.  x6 gets no gradient."""
+
+    @staticmethod
+    def forward(ctx, net, x6, *params):
+        keep = {}
+        w1, a1, b1, w2, a2, b2, occ = net.forward_train(x6, keep)
+        ops.softmax_channels_(w1)
+        ops.softmax_channels_(w2)
+        ctx.net, ctx.keep = net, keep
+        # in-place changes between forward and backward raise, as for torch layers
+        ctx.save_for_backward(*params, w1, a1, b1, w2, a2, b2, occ)
+        return w1, a1, b1, w2, a2, b2, occ
+
+    @staticmethod
+    def backward(ctx, *g):
+        net = ctx.net
+        w1, a1, b1, w2, a2, b2, occ = ctx.saved_tensors[-7:]
+        g = [t.contiguous() for t in g]
+        gl1, ga1, gb1 = ops.adacof_head_backward(g[0], g[1], g[2], w1, a1, b1)
+        gl2, ga2, gb2 = ops.adacof_head_backward(g[3], g[4], g[5], w2, a2, b2)
+        gz = ops.sigmoid_backward(g[6], occ)
+        names = [k for k, _ in net.named_parameters()]
+        need = {k: bool(f) for k, f in zip(names, ctx.needs_input_grad[2:])}
+        grads = net.backward_train(ctx.keep, (gl1, ga1, gb1, gl2, ga2, gb2, gz), need)
+        ctx.keep = None
+        return (None, None, *[grads.get(k) if need[k] else None for k in names])
 
 
 class AdaCoFNet(torch.nn.Module):

@@ -270,9 +270,11 @@ def packed_transposed(weight):
     return PackedConv(weight.detach().transpose(0, 1).flip(2, 3))
 
 
-def conv2d_backward_weight(x, dy, ks, pad_mode="zeros", bias=True):
+def conv2d_backward_weight(x, dy, ks, pad_mode="zeros", bias=True, max_splits=None):
     """(dW (Cout, Cin, KS, KS), dbias (Cout) or None) of a stride-1 conv2d layer with input x and output gradient dy.
-    One vfi_conv2d_backward_weight call (split-K partial slabs in the per-stream workspace, fixed-order reduction)."""
+    One vfi_conv2d_backward_weight call (split-K partial slabs in the per-stream workspace, fixed-order reduction).
+    `max_splits` caps the split count (by the workspace size handed on): two calls over the same pixels with the same
+    split count sum in the same order, whatever their Cout -- see conv2d_backward_weight_splits."""
     n, cin, h, w = x.shape
     cout = dy.shape[1]
     if tuple(dy.shape) != (n, cout, h, w):
@@ -283,9 +285,17 @@ def conv2d_backward_weight(x, dy, ks, pad_mode="zeros", bias=True):
     gp, gs = _slice_ptr(dy, "dy")
     ws = _workspace(x.device)
     work = ("flop", 2.0 * n * cin * cout * ks * ks * h * w, f"conv_wgrad_kernel<{ks}>") if _lib.PROFILE is not None else None
+    ws_floats = ws.numel()
+    if max_splits is not None:
+        ws_floats = min(ws_floats, max(int(max_splits), 1) * cout * (cin * ks * ks + 1))
     _lib.call("vfi_conv2d_backward_weight", xp, xs, gp, gs, dw.data_ptr(), db.data_ptr() if bias else None, n, cin, h, w,
-              cout, ks, PAD[pad_mode], ws.data_ptr(), ws.numel(), _lib.stream_ptr(), work=work)
+              cout, ks, PAD[pad_mode], ws.data_ptr(), ws_floats, _lib.stream_ptr(), work=work)
     return dw, db
+
+
+def conv2d_backward_weight_splits(n, cin, h, w, cout, ks):
+    """Split count vfi_conv2d_backward_weight uses for this layer with the default workspace (the library's rule)."""
+    return int(_lib.lib().vfi_conv2d_backward_weight_splits(n, cin, h, w, cout, ks, WORKSPACE_FLOATS))
 
 
 BWD_DATA_SPLITK_FLOATS = 8 * 1024 * 1024     # handed on to vfi_conv2d's split-K beyond the embed / fold buffers
@@ -355,6 +365,157 @@ def resize_bilinear_backward(x, grad, relu_input=True, out=None):
               int(bool(relu_input)), _lib.stream_ptr(),
               work=("byte", 4.0 * n * c * h * w * 6, "resize_bilinear_backward") if _lib.PROFILE is not None else None)
     return out
+
+
+# ---- glue of the AdaCoF network's backward ---------------------------------------------------
+def _prof(kind, amount, label):
+    return (kind, amount, label) if _lib.PROFILE is not None else None
+
+
+def add(a, b):
+    """a + b as a new dense tensor (operands may be channel slices)."""
+    n = a.shape[0]
+    count = a[0].numel()
+    if tuple(a.shape) != tuple(b.shape):
+        raise VfiLibraryError("add: shape mismatch")
+    out = new(tuple(a.shape), a)
+    ap, as_ = _slice_ptr(a, "a")
+    bp, bs = _slice_ptr(b, "b")
+    _lib.call("vfi_add", ap, as_, bp, bs, out.data_ptr(), count, n, count, _lib.stream_ptr(),
+              work=_prof("byte", 12.0 * n * count, "add"))
+    return out
+
+
+def relu_mask_(grad, y, addend=None, out=None):
+    """(grad + addend) * [y > 0], in place unless `out` is given; y is the ReLU's output."""
+    n = grad.shape[0]
+    count = grad[0].numel()
+    if tuple(y.shape) != tuple(grad.shape) or (addend is not None and tuple(addend.shape) != tuple(grad.shape)):
+        raise VfiLibraryError("relu_mask_: shape mismatch")
+    gp, gs = _slice_ptr(grad, "grad")
+    yp, ys = _slice_ptr(y, "y")
+    ap, as_ = (None, 0) if addend is None else _slice_ptr(addend, "addend")
+    op, os_ = (gp, gs) if out is None else _slice_ptr(out, "out")
+    if out is not None and tuple(out.shape) != tuple(grad.shape):
+        raise VfiLibraryError("relu_mask_: out shape mismatch")
+    _lib.call("vfi_relu_mask", gp, gs, ap, as_, yp, ys, op, os_, n, count, _lib.stream_ptr(),
+              work=_prof("byte", 4.0 * n * count * (3 + (addend is not None)), "relu_mask"))
+    return grad if out is None else out
+
+
+def sigmoid_backward(grad, s):
+    """grad * s * (1 - s) for s = sigmoid(z)."""
+    gz = torch.empty_like(s)
+    _lib.call("vfi_sigmoid_backward", _lib.dptr(grad, "grad"), _lib.dptr(s, "s"), gz.data_ptr(), s.numel(), _lib.stream_ptr(),
+              work=_prof("byte", 12.0 * s.numel(), "sigmoid_backward"))
+    return gz
+
+
+def replicate_pad(x, pad):
+    """ReplicationPad2d(pad) of an NCHW tensor (dense result)."""
+    n, c, h, w = x.shape
+    out = new((n, c, h + 2 * pad, w + 2 * pad), x)
+    xp, xs = _slice_ptr(x, "x")
+    _lib.call("vfi_replicate_pad", xp, xs, out.data_ptr(), n, c, h, w, int(pad), _lib.stream_ptr(),
+              work=_prof("byte", 4.0 * (x.numel() + out.numel()), "replicate_pad"))
+    return out
+
+
+def pool2_avg_backward(y, grad_pooled, grad_skip=None, out=None):
+    """Gradient of y = relu(z) feeding AvgPool2d(2) and a skip: (grad_pooled / 4 over each window + grad_skip) * [y > 0]."""
+    n, c, h, w = y.shape
+    if tuple(grad_pooled.shape) != (n, c, h // 2, w // 2) or (grad_skip is not None and tuple(grad_skip.shape) != tuple(y.shape)):
+        raise VfiLibraryError("pool2_avg_backward: shape mismatch")
+    if out is None:
+        out = new((n, c, h, w), y)
+    yp, ys = _slice_ptr(y, "y")
+    pp, ps = _slice_ptr(grad_pooled, "grad_pooled")
+    kp, ks = (None, 0) if grad_skip is None else _slice_ptr(grad_skip, "grad_skip")
+    op, os_ = _slice_ptr(out, "out")
+    _lib.call("vfi_pool2_avg_backward", yp, ys, pp, ps, kp, ks, op, os_, n, c, h, w, _lib.stream_ptr(),
+              work=_prof("byte", 4.0 * n * c * h * w * (2.25 + (grad_skip is not None)), "pool2_avg_backward"))
+    return out
+
+
+def upsample2x_backward(grad, mask_src=None, out=None):
+    """Adjoint of resize_bilinear(x, 2x size, align_corners=True); mask_src: the source when it is a ReLU's output."""
+    n, c, ho, wo = grad.shape
+    if ho % 2 or wo % 2:
+        raise VfiLibraryError(f"upsample2x_backward: odd gradient size {ho}x{wo}")
+    h, w = ho // 2, wo // 2
+    if mask_src is not None and tuple(mask_src.shape) != (n, c, h, w):
+        raise VfiLibraryError("upsample2x_backward: mask_src shape mismatch")
+    if out is None:
+        out = new((n, c, h, w), grad)
+    gp, gs = _slice_ptr(grad, "grad")
+    mp, ms = (None, 0) if mask_src is None else _slice_ptr(mask_src, "mask_src")
+    op, os_ = _slice_ptr(out, "out")
+    _lib.call("vfi_upsample2x_backward", gp, gs, mp, ms, op, os_, n, c, h, w, _lib.stream_ptr(),
+              work=_prof("byte", 4.0 * n * c * h * w * (5 + (mask_src is not None)), "upsample2x_backward"))
+    return out
+
+
+def _reduce_workspace(like):
+    return torch.empty(_lib.REDUCE_WORKSPACE_FLOATS, dtype=torch.float32, device=like.device)
+
+
+def adacof_smooth_forward(w1, a1, b1, w2, a2, b2, occ, epsilon=0.001):
+    """-> (m (N,4,H,W) = [m_Alpha1, m_Beta1, m_Alpha2, m_Beta2], terms (2,) = [g_Spatial, g_Occlusion])."""
+    n, ff, h, w = w1.shape
+    f = int(round(ff ** 0.5))
+    m = new((n, 4, h, w), w1)
+    out = new((2,), w1)
+    d = _lib.dptr
+    _lib.call("vfi_adacof_smooth_forward", d(w1, "w1"), d(a1, "a1"), d(b1, "b1"), d(w2, "w2"), d(a2, "a2"), d(b2, "b2"),
+              d(occ, "occ"), m.data_ptr(), _reduce_workspace(w1).data_ptr(), out.data_ptr(), n, f, h, w, float(epsilon),
+              _lib.stream_ptr(), work=_prof("byte", 4.0 * n * h * w * (6 * ff + 4 + 2 * 5), "adacof_smooth_forward"))
+    return m, out
+
+
+def adacof_blend_backward(grad_frame, t1, t2, occ, up_occ=None, epsilon=0.001):
+    """-> (grad_t1, grad_t2, grad_z) of frame1 = occ t1 + (1 - occ) t2 cropped to grad_frame's size, occ = sigmoid(z);
+    up_occ: 0-dim device tensor, the upstream gradient of g_Occlusion."""
+    n, c, h, w = t1.shape
+    h0, w0 = grad_frame.shape[2:]
+    g1, g2, gz = torch.empty_like(t1), torch.empty_like(t1), torch.empty_like(occ)
+    d = _lib.dptr
+    _lib.call("vfi_adacof_blend_backward", d(grad_frame, "grad_frame"), d(t1, "t1"), d(t2, "t2"), d(occ, "occ"),
+              d(up_occ, "up_occ"), g1.data_ptr(), g2.data_ptr(), gz.data_ptr(), n, c, h, w, int(h0), int(w0), float(epsilon),
+              _lib.stream_ptr(), work=_prof("byte", 4.0 * n * (c * (h0 * w0 + 4 * h * w) + 2 * h * w), "adacof_blend_backward"))
+    return g1, g2, gz
+
+
+def adacof_head_backward(gw, ga, gb, w, a, b, m_a=None, m_b=None, up_spatial=None, epsilon=0.001):
+    """One side: (grad_logit, grad_alpha, grad_beta) from the sampler's gradients and g_Spatial's upstream gradient
+    (0-dim device tensor, or None); m_a, m_b: that side's planes m[:, i:i+1] of adacof_smooth_forward."""
+    n, ff, h, wd = w.shape
+    f = int(round(ff ** 0.5))
+    gl, gal, gbe = torch.empty_like(w), torch.empty_like(w), torch.empty_like(w)
+    d = _lib.dptr
+    map_, mbs = (None, 0) if m_a is None else _slice_ptr(m_a, "m_a")
+    mbp, _ = (None, 0) if m_b is None else _slice_ptr(m_b, "m_b")
+    _lib.call("vfi_adacof_head_backward", d(gw, "gw"), d(ga, "ga"), d(gb, "gb"), d(w, "w"), d(a, "a"), d(b, "b"), map_, mbp, mbs,
+              d(up_spatial, "up_spatial"), gl.data_ptr(), gal.data_ptr(), gbe.data_ptr(), n, f, h, wd, float(epsilon),
+              _lib.stream_ptr(), work=_prof("byte", 4.0 * n * h * wd * (9 * ff + 2), "adacof_head_backward"))
+    return gl, gal, gbe
+
+
+def charbonnier_forward(a, b=None, epsilon=0.001):
+    """mean(sqrt((a - b)^2 + epsilon^2)) -> 0-dim tensor."""
+    out = new((1,), a)
+    _lib.call("vfi_charbonnier_forward", _lib.dptr(a, "a"), _lib.dptr(b, "b"), a.numel(), float(epsilon),
+              _reduce_workspace(a).data_ptr(), out.data_ptr(), _lib.stream_ptr(),
+              work=_prof("byte", 4.0 * a.numel() * (1 + (b is not None)), "charbonnier_forward"))
+    return out[0]
+
+
+def charbonnier_backward(a, b, upstream, epsilon=0.001, need_a=True, need_b=False):
+    ga = torch.empty_like(a) if need_a else None
+    gb = torch.empty_like(a) if need_b else None
+    _lib.call("vfi_charbonnier_backward", _lib.dptr(a, "a"), _lib.dptr(b, "b"), _lib.dptr(upstream.reshape(1), "upstream"),
+              _lib.dptr(ga), _lib.dptr(gb), a.numel(), float(epsilon), _lib.stream_ptr(),
+              work=_prof("byte", 4.0 * a.numel() * (1 + (b is not None) + need_a + need_b), "charbonnier_backward"))
+    return ga, gb
 
 
 def _out_like(x, out, name):

@@ -298,6 +298,11 @@ int vfi_conv2d_backward_weight(const float *x, long long x_bstride, const float 
                                float *dbias, int N, int Cin, int H, int W, int Cout, int KS, int pad_mode, float *workspace,
                                long long workspace_floats, vfi_stream_t stream);
 
+/* Number of partial slabs vfi_conv2d_backward_weight sums for this layer and workspace (-1 on bad arguments).  Two calls
+ * over the same (N, H, W) with the same count accumulate every element in the same order, whatever their Cout: a bank of
+ * filters (the AdaCoF heads' shared 64 -> 448 first convolution) then gives the bits of its members' own calls. */
+int vfi_conv2d_backward_weight_splits(int N, int Cin, int H, int W, int Cout, int KS, long long workspace_floats);
+
 /* Minimum workspace (floats) of vfi_conv2d_backward_data (-1 on bad arguments): N*(Cin+Cout)*(H+2p)*(W+2p) for
  * reflect padding p = (KS-1)/2 > 0, else 0. */
 long long vfi_conv2d_backward_data_workspace_floats(int N, int Cin, int H, int W, int Cout, int KS, int pad_mode);
@@ -329,6 +334,84 @@ int vfi_pool2_max_backward(const float *y, long long y_bstride, const float *gra
 int vfi_resize_bilinear_backward(const float *x, long long x_bstride, const float *grad_y, long long gy_bstride,
                                  float *grad_x, long long gx_bstride, int N, int C, int Hin, int Win, int Hout, int Wout,
                                  int relu_input, vfi_stream_t stream);
+
+/* ------------------------------------------------------------------------------------
+ * Backward of the plain AdaCoF network (training, src/adacof/trainer.py:36-54): the glue between the convolution
+ * gradients above and vfi_adacof_backward.  Differentiates src/adacof/models/adacofnet.py:13-153 (KernelEstimation) and
+ * :191-217 (blend, smoothness terms) and src/adacof/utility.py:67-77 (Charbonnier).  Same rules: no float atomics, one
+ * writer per element, reductions in an order fixed by the shape.  Operands with a batch stride may be channel slices.
+ * ---------------------------------------------------------------------------------- */
+
+/* Floats of the `workspace` of the two reductions below. */
+#define VFI_REDUCE_WORKSPACE_FLOATS 4096
+
+/* out = a + b over N blocks of `count` floats: the additive skip of adacofnet.py:128-146, which the training forward keeps
+ * apart from relu(conv) so that the ReLU's mask stays exact. */
+int vfi_add(const float *a, long long a_bstride, const float *b, long long b_bstride, float *out, long long out_bstride,
+            int N, long long count, vfi_stream_t stream);
+
+/* out = (grad + addend) * [y > 0] (ReLU backward between the convolutions of a block, adacofnet.py:14-23; y is the ReLU's
+ * output, y == 0 passes nothing).  addend may be NULL; out may be grad itself (in place). */
+int vfi_relu_mask(const float *grad, long long g_bstride, const float *addend, long long a_bstride, const float *y,
+                  long long y_bstride, float *out, long long out_bstride, int N, long long count, vfi_stream_t stream);
+
+/* grad_z = grad * s * (1 - s): backward of s = sigmoid(z) over `count` floats (the occlusion head, adacofnet.py:98-99, when
+ * KernelEstimation is trained on its own; AdaCoFNet's backward folds it into vfi_adacof_blend_backward). */
+int vfi_sigmoid_backward(const float *grad, const float *s, float *grad_z, long long count, vfi_stream_t stream);
+
+/* out (N, C, H + 2 pad, W + 2 pad) dense = ReplicationPad2d(pad) of x (N, C, H, W) (adacofnet.py:166,193-194): the planar
+ * padded frames vfi_adacof_backward reads. */
+int vfi_replicate_pad(const float *x, long long x_bstride, float *out, int N, int C, int H, int W, int pad,
+                      vfi_stream_t stream);
+
+/* Backward of an encoder block's glue (adacofnet.py:112-125): y = relu(conv) (N, C, H, W) feeds AvgPool2d(2) and the skip.
+ * grad_y = (0.25 * grad_pooled over its 2x2 window + grad_skip) * [y > 0].  grad_skip may be NULL.  H, W even; operands
+ * 8-byte aligned with even batch strides. */
+int vfi_pool2_avg_backward(const float *y, long long y_bstride, const float *grad_pooled, long long gp_bstride,
+                           const float *grad_skip, long long gs_bstride, float *grad_y, long long gy_bstride, int N, int C,
+                           int H, int W, vfi_stream_t stream);
+
+/* Adjoint of Upsample(scale_factor=2, bilinear, align_corners=True) (adacofnet.py:30,42,54,68,76,88), gather form:
+ * grad_x (N, C, Hin, Win) from grad_y (N, C, 2 Hin, 2 Win) with the weights of align_corners=1 from exact integer cell / remainder arithmetic
+ * (Hin = 1 or Win = 1: every output reads source 0).  mask_src (may be NULL) is the upsample's source when it is a ReLU's
+ * output: grad_x is multiplied by [mask_src > 0]. */
+int vfi_upsample2x_backward(const float *grad_y, long long gy_bstride, const float *mask_src, long long ms_bstride,
+                            float *grad_x, long long gx_bstride, int N, int C, int Hin, int Win, vfi_stream_t stream);
+
+/* Smoothness terms of adacofnet.py:204-215.  w*, a*, b* (N, F*F, H, W) dense (w* after the softmax), occ (N, 1, H, W).
+ *   m (N, 4, H, W) <- (mean_k W1 A1, mean_k W1 B1, mean_k W2 A2, mean_k W2 B2)   [m_Alpha1, m_Beta1, m_Alpha2, m_Beta2]
+ *   out[0] = g_Spatial, out[1] = g_Occlusion with CharbonnierFunc(d) = mean sqrt(d^2 + epsilon^2) of the horizontal plus
+ *   that of the vertical differences.  Two-stage reduction over `workspace` (VFI_REDUCE_WORKSPACE_FLOATS). */
+int vfi_adacof_smooth_forward(const float *w1, const float *a1, const float *b1, const float *w2, const float *a2,
+                              const float *b2, const float *occ, float *m, float *workspace, float *out, int N, int F,
+                              int H, int W, float epsilon, vfi_stream_t stream);
+
+/* Backward of frame1 = occ t1 + (1 - occ) t2 cropped to (h0, w0) (adacofnet.py:196-200) and of g_Occlusion (:213), through
+ * the sigmoid that made occ.  grad_frame (N, C, h0, w0) dense; t1, t2 (N, C, H, W); occ (N, 1, H, W); up_occ: device
+ * scalar, the upstream gradient of g_Occlusion (NULL: none).
+ *   grad_t1 = g occ, grad_t2 = g (1 - occ), grad_z = (sum_c g_c (t1_c - t2_c) + up_occ * dCharbonnier/d occ) occ (1 - occ)
+ * with g = grad_frame inside the crop and 0 outside. */
+int vfi_adacof_blend_backward(const float *grad_frame, const float *t1, const float *t2, const float *occ,
+                              const float *up_occ, float *grad_t1, float *grad_t2, float *grad_z, int N, int C, int H,
+                              int W, int h0, int w0, float epsilon, vfi_stream_t stream);
+
+/* One side's head gradients from vfi_adacof_backward's (gw, ga, gb) and g_Spatial (adacofnet.py:204-212,215).  m_a, m_b:
+ * that side's two planes of vfi_adacof_smooth_forward's m (batch stride m_bstride); up_spatial: device scalar (NULL: none).
+ * With q_X = up_spatial * dCharbonnier/d m_X:  gW_k = gw_k + (q_A a_k + q_B b_k) / F^2,
+ *   grad_logit_k = w_k (gW_k - sum_j w_j gW_j)  (softmax backward),  grad_alpha_k = ga_k + q_A w_k / F^2,  grad_beta alike. */
+int vfi_adacof_head_backward(const float *gw, const float *ga, const float *gb, const float *w, const float *a,
+                             const float *b, const float *m_a, const float *m_b, long long m_bstride,
+                             const float *up_spatial, float *grad_logit, float *grad_alpha, float *grad_beta, int N, int F,
+                             int H, int W, float epsilon, vfi_stream_t stream);
+
+/* out[0] = mean sqrt((a - b)^2 + epsilon^2) over `count` floats (utility.py:67-77; b may be NULL = 0).  Two-stage
+ * reduction over `workspace` (VFI_REDUCE_WORKSPACE_FLOATS). */
+int vfi_charbonnier_forward(const float *a, const float *b, long long count, float epsilon, float *workspace, float *out,
+                            vfi_stream_t stream);
+
+/* grad_a = upstream[0] * d / sqrt(d^2 + epsilon^2) / count with d = a - b, grad_b = -grad_a; either may be NULL. */
+int vfi_charbonnier_backward(const float *a, const float *b, const float *upstream, float *grad_a, float *grad_b,
+                             long long count, float epsilon, vfi_stream_t stream);
 
 /* ------------------------------------------------------------------------------------
  * Complex steerable pyramid (frequency domain), scale_factor-generalised
