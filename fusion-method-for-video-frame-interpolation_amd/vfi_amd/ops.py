@@ -518,6 +518,111 @@ def charbonnier_backward(a, b, upstream, epsilon=0.001, need_a=True, need_b=Fals
     return ga, gb
 
 
+# ---- glue of a PhaseNet level's backward -----------------------------------------------------
+def resize_bilinear_adjoint(grad, size, out=None):
+    """Adjoint of resize_bilinear(x, grad's size, align_corners=False) for x of spatial `size` (any sizes; gather form)."""
+    n, c, ho, wo = grad.shape
+    h, w = size
+    if out is None:
+        out = new((n, c, h, w), grad)
+    elif tuple(out.shape) != (n, c, h, w):
+        raise VfiLibraryError(f"resize_bilinear_adjoint: out shape {tuple(out.shape)} != {(n, c, h, w)}")
+    gp, gs = _slice_ptr(grad, "grad")
+    op, os_ = _slice_ptr(out, "out")
+    _lib.call("vfi_resize_bilinear_adjoint", gp, gs, op, os_, n, c, int(h), int(w), ho, wo, _lib.stream_ptr(),
+              work=_prof("byte", 4.0 * n * c * (h * w + ho * wo), "resize_bilinear_adjoint"))
+    return out
+
+
+def act_backward_(grad, y, act, out=None):
+    """grad * f'(y) from the activation's output y, act in 'elu' | 'tanh'; in place unless `out` is given."""
+    n = grad.shape[0]
+    count = grad[0].numel()
+    if act not in ("elu", "tanh"):
+        raise VfiLibraryError(f"act_backward_: no backward for activation {act!r}")
+    if tuple(y.shape) != tuple(grad.shape) or (out is not None and tuple(out.shape) != tuple(grad.shape)):
+        raise VfiLibraryError("act_backward_: shape mismatch")
+    gp, gs = _slice_ptr(grad, "grad")
+    yp, ys = _slice_ptr(y, "y")
+    op, os_ = (gp, gs) if out is None else _slice_ptr(out, "out")
+    _lib.call("vfi_act_backward", gp, gs, yp, ys, op, os_, n, count, ACT[act], _lib.stream_ptr(),
+              work=_prof("byte", 12.0 * n * count, "act_backward"))
+    return grad if out is None else out
+
+
+def phasenet_emit(pred, amp_in, max_amp):
+    """One band level's outputs (vfi_phasenet_emit): pred (N,8,H,W), amp_in (N,8,H,W) normalised amplitudes, max_amp (N,)
+    -> (phase, amp), each (N*4,1,H,W) in the per-image layout colour*4+band."""
+    n, c, h, w = pred.shape
+    if c != 8 or tuple(amp_in.shape) != (n, 8, h, w) or max_amp.numel() != n:
+        raise VfiLibraryError("phasenet_emit: pred and amp_in must be (N,8,H,W), max_amp (N,)")
+    pp, ps = _slice_ptr(pred, "pred")
+    ap, as_ = _slice_ptr(amp_in, "amp_in")
+    phase, amp = new((n * 4, 1, h, w), pred), new((n * 4, 1, h, w), pred)
+    _lib.call("vfi_phasenet_emit", pp, ps, ap, as_, _lib.dptr(max_amp, "max_amp"), phase.data_ptr(), amp.data_ptr(), n, h * w,
+              _lib.stream_ptr())
+    return phase, amp
+
+
+def phasenet_emit_backward(grad_phase, grad_amp, amp_in, max_amp):
+    """grad of phasenet_emit's pred (N,8,H,W) from the gradients of its outputs (either may be None = zero)."""
+    n, _, h, w = amp_in.shape
+    g = grad_phase if grad_phase is not None else grad_amp
+    if g is None or g.numel() != n * 4 * h * w:
+        raise VfiLibraryError("phasenet_emit_backward: gradient shape mismatch")
+    ap, as_ = _slice_ptr(amp_in, "amp_in")
+    out = new((n, 8, h, w), amp_in)
+    _lib.call("vfi_phasenet_emit_backward", _lib.dptr(grad_phase, "grad_phase"), _lib.dptr(grad_amp, "grad_amp"), ap, as_,
+              _lib.dptr(max_amp, "max_amp"), out.data_ptr(), out.stride(0), n, h * w, _lib.stream_ptr(),
+              work=_prof("byte", 4.0 * n * h * w * 24, "phasenet_emit_backward"))
+    return out
+
+
+def phasenet_emit_low(pred, low_in, max_low):
+    """The low level's output (vfi_phasenet_emit_low): pred (N,1,H,W), low_in (N,2,H,W) normalised, max_low (N,) -> (N,1,H,W)."""
+    n, c, h, w = pred.shape
+    if c != 1 or tuple(low_in.shape) != (n, 2, h, w) or max_low.numel() != n:
+        raise VfiLibraryError("phasenet_emit_low: pred must be (N,1,H,W), low_in (N,2,H,W), max_low (N,)")
+    pp, ps = _slice_ptr(pred, "pred")
+    lp, ls = _slice_ptr(low_in, "low_in")
+    low = new((n, 1, h, w), pred)
+    _lib.call("vfi_phasenet_emit_low", pp, ps, lp, ls, _lib.dptr(max_low, "max_low"), low.data_ptr(), n, h * w,
+              _lib.stream_ptr())
+    return low
+
+
+def phasenet_emit_low_backward(grad_low, low_in, max_low):
+    n, _, h, w = low_in.shape
+    if grad_low.numel() != n * h * w:
+        raise VfiLibraryError("phasenet_emit_low_backward: gradient shape mismatch")
+    lp, ls = _slice_ptr(low_in, "low_in")
+    out = new((n, 1, h, w), low_in)
+    _lib.call("vfi_phasenet_emit_low_backward", _lib.dptr(grad_low, "grad_low"), lp, ls, _lib.dptr(max_low, "max_low"),
+              out.data_ptr(), out.stride(0), n, h * w, _lib.stream_ptr(),
+              work=_prof("byte", 4.0 * n * h * w * 4, "phasenet_emit_low_backward"))
+    return out
+
+
+def l1_forward(a, b, wrap=False, scale=1.0):
+    """scale * mean |w(a - b)| -> 0-dim tensor; w = atan2(sin, cos) when wrap (the phase loss), else the identity."""
+    if a.numel() != b.numel():
+        raise VfiLibraryError("l1_forward: shape mismatch")
+    out = new((1,), a)
+    _lib.call("vfi_l1_forward", _lib.dptr(a, "a"), _lib.dptr(b, "b"), a.numel(), int(bool(wrap)), float(scale),
+              _reduce_workspace(a).data_ptr(), out.data_ptr(), _lib.stream_ptr(),
+              work=_prof("byte", 8.0 * a.numel(), "l1_forward"))
+    return out[0]
+
+
+def l1_backward(a, b, upstream, wrap=False, scale=1.0, need_a=True, need_b=True):
+    ga = torch.empty_like(a) if need_a else None
+    gb = torch.empty_like(b) if need_b else None
+    _lib.call("vfi_l1_backward", _lib.dptr(a, "a"), _lib.dptr(b, "b"), _lib.dptr(upstream.reshape(1), "upstream"),
+              _lib.dptr(ga), _lib.dptr(gb), a.numel(), int(bool(wrap)), float(scale), _lib.stream_ptr(),
+              work=_prof("byte", 4.0 * a.numel() * (2 + need_a + need_b), "l1_backward"))
+    return ga, gb
+
+
 def _out_like(x, out, name):
     """`out`: None (a new tensor) or a contiguous tensor of x's shape the op writes into (a slice of a wider buffer: no
     concat copy afterwards)."""

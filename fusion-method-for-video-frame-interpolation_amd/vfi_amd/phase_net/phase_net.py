@@ -23,7 +23,10 @@ from ..values import DecompValues, NormalizedValues
 
 
 class PhaseNetBlock(torch.nn.Module):
-    """Parameter holder with the reference's key names (phase_net.py:179-200)."""
+    """The reference's block with its key names (phase_net.py:179-207, block.py:4-32).  PhaseNet.forward runs the blocks
+    through its own permuted packs; `forward` here is the reference's `(f, c) = block(x)` on an input in the reference's
+    channel order, differentiable with a HIP backward.  BatchNorm uses its running statistics: a new
+    block is in eval mode, and a block switched to training mode refuses to run (batch statistics are not built)."""
 
     def __init__(self, c_in, c_out, pred_out, kernel_size, device=None, dropout=0.5):
         super().__init__()
@@ -31,6 +34,13 @@ class PhaseNetBlock(torch.nn.Module):
         self.feature_map = Indexed({0: ConvParams(c_in, c_out, k), 1: BatchNormParams(c_out),
                                     3: ConvParams(c_out, c_out, k)})
         self.prediction_map = Indexed({0: ConvParams(c_out, pred_out, 1)})
+        self.train(False)
+        if device is not None:
+            self.to(device)
+
+    def forward(self, x):
+        from .grad import block_forward
+        return block_forward(self, x)
 
 
 class PhaseNet(PackedModule):

@@ -414,6 +414,49 @@ int vfi_charbonnier_backward(const float *a, const float *b, const float *upstre
                              long long count, float epsilon, vfi_stream_t stream);
 
 /* ------------------------------------------------------------------------------------
+ * Backward of one PhaseNet level (training, src/phase_net/train.py with src/train/loss.py): the glue between the
+ * convolution gradients above.  Differentiates src/phase_net/phase_net.py:113-116,138-139,155-168,190-200 with
+ * reverse_normalize :80-98, and src/train/loss.py:10-20.  Same rules: no float atomics, one writer per element,
+ * reductions in an order fixed by the shape, fp32.  Operands with a batch stride may be channel slices.
+ * ---------------------------------------------------------------------------------- */
+
+/* Adjoint of vfi_resize_bilinear with align_corners = 0, relu_input = 0 and no residual, for any sizes >= 1 (up- and
+ * down-sampling): nn.Upsample((res1, res2), mode='bilinear') of phase_net.py:138-139.  Gather form: grad_x (N, C, Hin, Win)
+ * element s sums grad_y (N, C, Hout, Wout) over the outputs whose forward taps hit s, found by re-evaluating the forward's
+ * own fp32 index and weight arithmetic over a candidate range, rows outermost, both ascending.  A source that no output
+ * reads gets 0.  Sizes below 2^20. */
+int vfi_resize_bilinear_adjoint(const float *grad_y, long long gy_bstride, float *grad_x, long long gx_bstride, int N, int C,
+                                int Hin, int Win, int Hout, int Wout, vfi_stream_t stream);
+
+/* out = grad * f'(y) over N blocks of `count` floats, from the activation's OUTPUT y (phase_net.py:193,195,199):
+ * act = VFI_ACT_ELU (alpha = 1): f' = y > 0 ? 1 : y + 1;  VFI_ACT_TANH: f' = 1 - y^2.  out may be grad itself (in place). */
+int vfi_act_backward(const float *grad, long long g_bstride, const float *y, long long y_bstride, float *out,
+                     long long out_bstride, int N, long long count, int act, vfi_stream_t stream);
+
+/* Adjoint of vfi_phasenet_emit with respect to pred (phase_net.py:155-168, :80-90).  grad_phase, grad_amp (N, 4, HW) dense,
+ * either may be NULL (= zero); amp_in, max_amp as in the forward (they get no gradient):
+ *   grad_pred[:, 0:4] = pi * grad_phase;  grad_pred[:, 4:8] = grad_amp * max_amp[n] * (amp_in[:, 4:8] - amp_in[:, 0:4]) / 2. */
+int vfi_phasenet_emit_backward(const float *grad_phase, const float *grad_amp, const float *amp_in, long long amp_bstride,
+                               const float *max_amp, float *grad_pred, long long gp_bstride, int N, int HW,
+                               vfi_stream_t stream);
+
+/* Adjoint of vfi_phasenet_emit_low with respect to pred (phase_net.py:113-116, :96-98): grad_low (N, HW) dense,
+ *   grad_pred (N, HW) = grad_low * max_low[n] * (low_in[:, 0] - low_in[:, 1]) / 2. */
+int vfi_phasenet_emit_low_backward(const float *grad_low, const float *low_in, long long low_bstride, const float *max_low,
+                                   float *grad_pred, long long gp_bstride, int N, int HW, vfi_stream_t stream);
+
+/* out[0] = scale / count * sum |w(a - b)| over `count` floats, w(d) = atan2(sin d, cos d) when wrap != 0, else d.
+ * wrap = 0, scale = 1: nn.L1Loss (loss.py:8,20).  wrap = 1, scale = nbands, a = the target's and b = the output's phases
+ * of one level: that level's term of the phase loss, the sum over the orientations of the mean |delta_psi| (loss.py:10-16).
+ * Two-stage reduction over `workspace` (VFI_REDUCE_WORKSPACE_FLOATS), tree fixed by `count`. */
+int vfi_l1_forward(const float *a, const float *b, long long count, int wrap, float scale, float *workspace, float *out,
+                   vfi_stream_t stream);
+
+/* grad_a = sign(w(a - b)) * upstream[0] * scale / count, grad_b = -grad_a; either may be NULL. */
+int vfi_l1_backward(const float *a, const float *b, const float *upstream, float *grad_a, float *grad_b, long long count,
+                    int wrap, float scale, vfi_stream_t stream);
+
+/* ------------------------------------------------------------------------------------
  * Complex steerable pyramid (frequency domain), scale_factor-generalised
  * ---------------------------------------------------------------------------------- */
 
