@@ -1,7 +1,7 @@
 // Internal interface between vfi_pyr_plan.hip (the plan: mask tables, transform tables and every level's resolved passes,
 // all built at vfi_pyr_plan_create) and vfi_pyramid.hip (the kernels and the calls that run on a plan).  After creation a
 // call reads the plan through `const` access and writes the workspace only; vfi_pyr_plan_prepare_filter /
-// vfi_pyr_plan_prepare_adjoint add tables, as include/vfi_hip.h documents.
+// vfi_pyr_plan_prepare_adjoint / vfi_pyr_plan_prepare_analysis_adjoint add tables, as include/vfi_hip.h documents.
 #pragma once
 #include "vfi_common.h"
 #include "vfi_fft.h"
@@ -31,6 +31,7 @@ struct Level : Size2D {        // h x w: the level's window of the spectrum
     float *P_s;                // [nb][h][w] synthesis : angle mask (two sided) * himask
     float *lomask;             // [h2][w2]  low-pass applied to the NEXT level's window, unshifted order of that window
     float *A = nullptr;        // [nb][h][w] synthesis adjoint: lo0 * prod_{j<k} lomask_j * P_s (vfi_pyr_plan_prepare_adjoint)
+    float *B = nullptr;        // [nb][h][w] analysis adjoint: himask_k * angle mask (one sided) * H W / (h w) (vfi_pyr_plan_prepare_analysis_adjoint)
     int tpitch_ana, tpitch_syn;   // row pitch of T: w rounded up to 16 when both passes run on the wave engine (the generic kernels address T densely)
     int tile, bands;           // generic-engine column pass: columns per workgroup, bands per transform call
 };
@@ -60,4 +61,5 @@ struct vfi_pyr_plan {
     std::vector<double> log_rad, xr0, yr, yir;
     std::vector<float *> filters;   // [id] -> H x (W/2+1) radial gain tables
     bool adjoint = false;           // Level::A built (vfi_pyr_plan_prepare_adjoint)
+    bool analysis_adjoint = false;  // Level::B built (vfi_pyr_plan_prepare_analysis_adjoint)
 };

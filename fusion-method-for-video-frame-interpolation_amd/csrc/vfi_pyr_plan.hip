@@ -423,3 +423,49 @@ extern "C" int vfi_pyr_plan_prepare_adjoint(vfi_pyr_plan *p) {
     p->adjoint = true;
     return VFI_OK;
 }
+
+// B_k[b] = himask_k * one-sided angle mask b * (H W) / (h_k w_k) on level k's window (unshifted order).  The analysis is
+// z_{k,b} = 1/(h_k w_k) * IFFT2_k,unnormalised(i * window_k(FFT2(x)) * P_a[k][b]); its adjoint applied to coefficient gradients
+// G is  grad x = Re IFFT2,unnormalised( sum_k embed_k( (-i) * P_a[k][b] * FFT2_k(G_{k,b}) / (h_k w_k) ) )  -- the synthesis' passes.
+// P_a itself cannot stand in for the synthesis' P_s there: it carries lo0 * prod_{j<k} lomask_j, which the synthesis' column
+// pass and final kernel apply again on the way up (lomask_j at every embed, lo0 at the end), and not the constant that
+// turns the synthesis' final 1/(H W) into 1/(h_k w_k).  So B_k is P_a without that chain, times H W / (h_k w_k).
+extern "C" int vfi_pyr_plan_prepare_analysis_adjoint(vfi_pyr_plan *p) {
+    VFI_REQUIRE(p, VFI_ERR_INVALID_ARG, "vfi_pyr_plan_prepare_analysis_adjoint: null plan");
+    if (p->analysis_adjoint) return VFI_OK;
+    const int H = p->H, W = p->W, nb = p->nbands;
+    const std::vector<double> gy = linspace_grid(H), gx = linspace_grid(W);
+    std::vector<double> xc, ya, ys;
+    angle_luts(nb, xc, ya, ys);
+    std::vector<double> xcb(xc.size()), xr = p->xr0;
+    const double ls = std::log2(p->scale);
+    std::vector<std::vector<float>> tabs(p->nlev);
+    for (int k = 0; k < p->nlev; ++k) {
+        const Level &L = p->lev[k];
+        for (auto &x : xr) x -= ls;
+        const int h = L.h, w = L.w, sy = H / 2 - h / 2, sx = W / 2 - w / 2;
+        const double c = ((double)H * W) / ((double)h * w);
+        std::vector<double> g((size_t)h * w);      // himask_k (the oracle's float32 table) * H W / (h w)
+        for (int u = 0; u < h; ++u)
+            for (int v = 0; v < w; ++v) {
+                const size_t s = (size_t)(sy + shifted_of(u, h)) * W + (sx + shifted_of(v, w));
+                g[(size_t)u * w + v] = (double)(float)interp(p->log_rad[s], xr, p->yr) * c;
+            }
+        std::vector<float> &t = tabs[k];
+        t.resize((size_t)nb * h * w);
+        for (int b = 0; b < nb; ++b) {
+            for (size_t i = 0; i < xc.size(); ++i) xcb[i] = xc[i] + kPi * b / nb;
+            for (int u = 0; u < h; ++u)
+                for (int v = 0; v < w; ++v) {
+                    const int i = sy + shifted_of(u, h), j = sx + shifted_of(v, w);
+                    t[((size_t)b * h + u) * w + v] = (float)((double)(float)interp(std::atan2(gy[i], gx[j]), xcb, ya) * g[(size_t)u * w + v]);
+                }
+        }
+    }
+    for (int k = 0; k < p->nlev; ++k) {
+        const int rc = dev_upload(p, tabs[k], &p->lev[k].B);
+        if (rc) return vfi::fail(rc, "vfi_pyr_plan_prepare_analysis_adjoint: device allocation / upload failed");
+    }
+    p->analysis_adjoint = true;
+    return VFI_OK;
+}

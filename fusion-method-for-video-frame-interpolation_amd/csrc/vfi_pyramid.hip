@@ -19,7 +19,9 @@
 //               rotated, masked band spectra + embedded low-pass of the coarser level); levels without bands only embed
 //               (pyr_combine_kernel).
 //   backward  : vfi_pyr_synthesize_backward, the synthesis' adjoint = the analysis passes with the tables A_k (P_a with the
-//               synthesis' two-sided angle masks), the synthesis' 1/(H W), and a gradient epilogue on (phase, amplitude).
+//               synthesis' two-sided angle masks), the synthesis' 1/(H W), and a gradient epilogue on (phase, amplitude);
+//               vfi_pyr_analyze_backward, the analysis' adjoint = the synthesis passes with the tables B_k (the analysis'
+//               one-sided angle masks * himask * H W / (h w)) and a gradient prologue on (d phase, d amplitude).
 #include "vfi_pyr_plan.h"
 
 #include <cstdlib>
@@ -281,6 +283,7 @@ struct RowsPolarArgs {
     int groups;
 };
 // synthesis adjoint rows (vfi_pyr_synthesize_backward): phase / amp receive d phase / d amplitude, inv_hw = 1 / (H W)
+// analysis adjoint rows (vfi_pyr_analyze_backward): phase / amp hold d phase / d amplitude, phase_scale = s, inv_hw = 1 / s
 struct RowsPolarGradArgs : RowsPolarArgs {
     const float *fphase, *famp;   // the forward's (phase, amplitude), same layout (PlaneMap)
 };
@@ -437,8 +440,11 @@ __global__ void pyr_amp_max_finish_kernel(const unsigned *__restrict__ bits, flo
 
 // (phase, amplitude) rows -> complex -> forward row FFT -> T (values_to_coeff, src/train/pyramid.py:99-107, + the row half of
 // reconstruct's fft2)
-template <int NB, bool BLU>
-__global__ __launch_bounds__(kThreads, kThreads / 128) void pyr_rows_from_polar_kernel(const RowsPolarArgs a) {
+// GRAD: the prologue of the analysis adjoint instead -- the gradients (d phase, d amplitude) and the forward's (p, A) at the
+// same offset give the coefficient gradient G = (d A + i s d p / A) e^{i p / s} (s = phase scale); the d p term is dropped
+// where A == 0, where the phase has no gradient (atan2 at the origin).
+template <int NB, bool BLU, bool GRAD = false>
+__global__ __launch_bounds__(kThreads, kThreads / 128) void pyr_rows_from_polar_kernel(const RowsArgsOf<GRAD> a) {
     using namespace vfi::fft;
     extern __shared__ float2 buf[];
     const int w = a.pw.n, m = a.pw.m, pitch = padded_length(m);
@@ -455,12 +461,25 @@ __global__ __launch_bounds__(kThreads, kThreads / 128) void pyr_rows_from_polar_
     auto fill_load = [&](int l, int j) {
         const size_t o = base[l] + j;
         Slot s;
+        if constexpr (GRAD) {      // (the slot's chirp field carries the forward's values: the chirp factor is read at the use)
+            s.z = make_float2(a.phase[o], a.amp[o]);
+            s.c = make_float2(a.fphase[o], a.famp[o]);
+            return s;
+        }
         if (a.pm.complex_coeff) s.z = reinterpret_cast<const float2 *>(a.phase)[o];
         else s.z = make_float2(a.phase[o], a.amp[o]);
         if (blu) s.c = a.pw.chirp[j];
         return s;
     };
-    auto fill_use = [&](int idx, const Slot &s) {
+    auto fill_use = [&](int j, int idx, const Slot &s) {
+        if constexpr (GRAD) {
+            float sn, cs;
+            sincosf(s.c.x * a.inv_hw, &sn, &cs);
+            const float t = s.c.y > 0.0f ? a.phase_scale * s.z.x / s.c.y : 0.0f;
+            buf[idx] = load_value<false>(make_float2(s.z.y * cs - t * sn, s.z.y * sn + t * cs),
+                                         blu ? a.pw.chirp[j] : make_float2(0.0f, 0.0f), blu);
+            return;
+        }
         float2 x = s.z;
         if (!a.pm.complex_coeff) {
             float sn, cs;
@@ -479,10 +498,10 @@ __global__ __launch_bounds__(kThreads, kThreads / 128) void pyr_rows_from_polar_
     const bool wide = w >= kThreads;
     if (wide)
         for_rows(lines, w, pitch, [&](int l, int j, int) { return fill_load(l, j); },
-                 [&](int, int, int, int idx, const Slot &s) { fill_use(idx, s); });
+                 [&](int, int j, int, int idx, const Slot &s) { fill_use(j, idx, s); });
     else
         for_slots(total, [&](int e) { const int l = fast_div(e, inv_w); return fill_load(l, e - mul24(l, w)); },
-                  [&](int e, const Slot &s) { const int l = fast_div(e, inv_w); fill_use(mul24(l, pitch) + phys(e - mul24(l, w)), s); });
+                  [&](int e, const Slot &s) { const int l = fast_div(e, inv_w), j = e - mul24(l, w); fill_use(j, mul24(l, pitch) + phys(j), s); });
     if (blu) zero_row_padding(buf, lines, pitch, w, m);
     lds_barrier();
     fft_lines(buf, lines, pitch, a.pw, twl);
@@ -626,14 +645,14 @@ void debug_scan(const void *dev, size_t floats, hipStream_t s, const char *what,
 // ---- 2-D transforms = a row pass and a column pass, each on the wave engine where the plan resolved a configuration
 // for the length, otherwise on the generic LDS engine (vfi_fft.h / vfi_fft.hip) ------------------------------------------
 int pass_rows(const Size2D &z, const void *src, void *dst, long long rows, int src_pitch, int dst_pitch, vfi::fft::RowLoad load,
-              vfi::fft::RowStore store, bool inverse, hipStream_t s) {
+              vfi::fft::RowStore store, bool inverse, hipStream_t s, float scale = 1.0f) {
     using namespace vfi::fft;
     const vfi::pyrw::Tables &tb = z.wave[kWaveRows];
     if (tb.M && rows < (1LL << 31)) {
-        vfi::pyrw::GenRowsArgs a{tb, src, dst, (int)rows, src_pitch, dst_pitch, 1.0f};
+        vfi::pyrw::GenRowsArgs a{tb, src, dst, (int)rows, src_pitch, dst_pitch, scale};
         return vfi::pyrw::launch_gen_rows(a, (int)load, (int)store, inverse, s);      // (RowLoad / RowStore == GenRowKind values)
     }
-    RowArgs r{z.pw, src, dst, rows, src_pitch, dst_pitch, rows_per_group(z.pw, rows), 1.0f};
+    RowArgs r{z.pw, src, dst, rows, src_pitch, dst_pitch, rows_per_group(z.pw, rows), scale};
     return launch_rows(r, load, store, inverse, s);
 }
 int pass_cols(const Size2D &z, float2 *data, int planes, int cols, int ld, bool inverse, hipStream_t s) {
@@ -647,11 +666,11 @@ int pass_cols(const Size2D &z, float2 *data, int planes, int cols, int ld, bool 
     return launch_cols(c, inverse, s);
 }
 
-// in-place complex 2-D transform of `planes` dense z.h x z.w arrays (un-normalised)
-int fft2d_c2c(const Size2D &z, float2 *data, int planes, bool inverse, hipStream_t s) {
+// in-place complex 2-D transform of `planes` dense z.h x z.w arrays (un-normalised, times `scale`)
+int fft2d_c2c(const Size2D &z, float2 *data, int planes, bool inverse, hipStream_t s, float scale = 1.0f) {
     const int rc = pass_cols(z, data, planes, z.w, z.w, inverse, s);
     if (rc) return rc;
-    return pass_rows(z, data, data, (long long)planes * z.h, z.w, z.w, vfi::fft::kLoadComplex, vfi::fft::kStoreComplex, inverse, s);
+    return pass_rows(z, data, data, (long long)planes * z.h, z.w, z.w, vfi::fft::kLoadComplex, vfi::fft::kStoreComplex, inverse, s, scale);
 }
 // real H x W images -> half spectra N x H x (W/2+1)
 int fft2d_r2c(const vfi_pyr_plan *p, const float *img, float2 *half, int N, hipStream_t s) {
@@ -870,26 +889,92 @@ void syn_embed(const vfi_pyr_plan *p, int k, int N, const float2 *res, int h2, i
     hipLaunchKernelGGL((pyr_combine_kernel<4>), dim3(ceil_div(L.w, 256), L.h), dim3(256), 0, s, p->bands, res, cur, L.P_s, L.lomask, N, L.h, L.w,
                        h2, w2, 0);
 }
-int syn_rows(const vfi_pyr_plan *p, int k, int N, const float *phase, const float *amp, const PlaneMap &pm, hipStream_t s) {
+// What vfi_pyr_synthesize and vfi_pyr_analyze_backward ask of the synthesis passes.
+// adjoint: vfi_pyr_analyze_backward runs them on the analysis' adjoint: the level tables B_k in place of P_s (they hold the
+// H W / (h w) that turns the final 1 / (H W) into each level's 1 / (h w); the low residual gets its own on the way in), and
+// with (phase, amplitude) the gradient prologue of the row pass, which reads the forward's values
+struct SynthCall {
+    const float *high;
+    const float *const *phase, *const *amp;       // adjoint: d phase / d amplitude (or G with VFI_PYR_COMPLEX_COEFF)
+    const int *plane_index;
+    const float *low;
+    unsigned long long level_mask;
+    int flags;
+    bool adjoint = false;
+    const float *const *fphase = nullptr, *const *famp = nullptr;   // the forward's outputs per level (unused with VFI_PYR_COMPLEX_COEFF)
+    float phase_scale = 1.0f;
+    bool grad() const { return adjoint && !(flags & VFI_PYR_COMPLEX_COEFF); }      // gradient prologue on (d phase, d amplitude)
+};
+
+int syn_rows(const vfi_pyr_plan *p, int k, int N, const SynthCall &c, hipStream_t s) {
     const Level &L = p->lev[k];
     const long long rows = (long long)N * p->nbands * L.h;
-    const RowsPolarArgs g{L.pw, p->bands, const_cast<float *>(phase), const_cast<float *>(amp), pm, rows, L.h, level_row_lines(L.pw, rows),
-                          1.0f, 1.0f, nullptr, 1};
-    if (L.wave[kWaveRows].M) return vfi::pyrw::launch_rows_from_polar(wave_rows_args(L, L.tpitch_syn, N * p->nbands, g), s);
+    const bool grad = c.grad();
+    const RowsPolarGradArgs g{{L.pw, p->bands, const_cast<float *>(c.phase[k]), const_cast<float *>(c.amp ? c.amp[k] : nullptr),
+                               make_map(c.plane_index, k, N, p->nbands, c.flags), rows, L.h, level_row_lines(L.pw, rows),
+                               grad ? 1.0f / c.phase_scale : 1.0f, grad ? c.phase_scale : 1.0f, nullptr, 1},
+                              grad ? c.fphase[k] : nullptr, grad ? c.famp[k] : nullptr};
+    if (L.wave[kWaveRows].M) {
+        const vfi::pyrw::RowsArgs ra = wave_rows_args(L, L.tpitch_syn, N * p->nbands, g);
+        return grad ? vfi::pyrw::launch_rows_from_polar_grad(vfi::pyrw::RowsGradArgs{ra, g.fphase, g.famp}, s) : vfi::pyrw::launch_rows_from_polar(ra, s);
+    }
+    if (grad)
+        return launch_engine<pyr_rows_from_polar_kernel<4, true, true>, pyr_rows_from_polar_kernel<4, false, true>>(L.pw.bluestein, dim3(rows_blocks(g)),
+                                                                                                                rows_lds(g), s, g);
     return launch_engine<pyr_rows_from_polar_kernel<4, true>, pyr_rows_from_polar_kernel<4, false>>(L.pw.bluestein, dim3(rows_blocks(g)),
-                                                                                                    rows_lds(g), s, g);
+                                                                                                    rows_lds(g), s, static_cast<const RowsPolarArgs &>(g));
 }
 // cur = this level's bands + the embedded coarser spectrum res (h2 x w2)
-int syn_cols(const vfi_pyr_plan *p, int k, int N, const float2 *res, int h2, int w2, float2 *cur, hipStream_t s) {
+int syn_cols(const vfi_pyr_plan *p, int k, int N, const float *P, const float2 *res, int h2, int w2, float2 *cur, hipStream_t s) {
     const Level &L = p->lev[k];
     const vfi::pyrw::Tables &tb = L.wave[kWaveSynCols];
     if (tb.M) {
-        vfi::pyrw::SynColsArgs ca{tb, p->bands, L.tpitch_syn, L.P_s, res, L.lomask, cur, N, L.h, L.w, h2, w2};
+        vfi::pyrw::SynColsArgs ca{tb, p->bands, L.tpitch_syn, P, res, L.lomask, cur, N, L.h, L.w, h2, w2};
         return vfi::pyrw::launch_syn_cols(ca, s);
     }
-    const CombineColsArgs ca{L.ph, p->bands, res, cur, L.P_s, L.lomask, L.h, L.w, h2, w2, L.tile, L.bands};
+    const CombineColsArgs ca{L.ph, p->bands, res, cur, P, L.lomask, L.h, L.w, h2, w2, L.tile, L.bands};
     return launch_engine<pyr_combine_cols_kernel<4, true>, pyr_combine_cols_kernel<4, false>>(L.ph.bluestein, dim3(cols_blocks(L), N),
                                                                                               cols_lds(L), s, ca);
+}
+
+int pyr_synthesize_impl(const vfi_pyr_plan *p, const SynthCall &c, float *img, int N, const char *who, vfi_stream_t stream) {
+    VFI_REQUIRE(N >= 1 && N <= p->max_images, VFI_ERR_INVALID_ARG, "%s: N=%d (plan max %d)", who, N, p->max_images);
+    VFI_REQUIRE((c.phase && (c.amp || (c.flags & VFI_PYR_COMPLEX_COEFF))) || c.level_mask == 0, VFI_ERR_INVALID_ARG,
+                "%s: null phase/amp tables", who);
+    hipStream_t s = vfi::as_stream(stream);
+    const int H = p->H, W = p->W;
+    int rc;
+    // coarsest: res = FFT(low) (zeros when low is NULL); the adjoint's low residual carries 1 / (hL wL) where the final has 1 / (H W)
+    float2 *res = p->lod[p->nlev & 1];
+    {
+        const long long tot = (long long)N * p->low.h * p->low.w;
+        hipLaunchKernelGGL(real_to_complex_kernel, dim3(blocks_1d(tot)), dim3(256), 0, s, c.low, res, tot);
+        const float scale = c.adjoint ? (float)(((double)H * W) / ((double)p->low.h * p->low.w)) : 1.0f;
+        if (c.low && (rc = fft2d_c2c(p->low, res, N, false, s, scale))) return rc;
+    }
+    for (int k = p->nlev - 1; k >= 0; --k) {
+        const Size2D &next = k + 1 < p->nlev ? p->lev[k + 1] : p->low;
+        float2 *cur = p->lod[k & 1];
+        if (!((c.level_mask >> k) & 1ull)) {
+            syn_embed(p, k, N, res, next.h, next.w, cur, s);
+        } else {
+            VFI_REQUIRE(c.phase[k] && ((c.flags & VFI_PYR_COMPLEX_COEFF) || c.amp[k]), VFI_ERR_INVALID_ARG, "%s: null input for level %d", who, k);
+            VFI_REQUIRE(!c.grad() || (c.fphase[k] && c.famp[k]), VFI_ERR_INVALID_ARG, "%s: null forward output for level %d", who, k);
+            if ((rc = syn_rows(p, k, N, c, s)) || (rc = syn_cols(p, k, N, c.adjoint ? p->lev[k].B : p->lev[k].P_s, res, next.h, next.w, cur, s)))
+                return rc;
+        }
+        res = cur;
+    }
+    const float2 *hi_half = nullptr;
+    if (c.high) {
+        if ((rc = fft2d_r2c(p, c.high, p->half0, N, s))) return rc;
+        hi_half = p->half0;
+    }
+    hipLaunchKernelGGL(pyr_final_kernel, dim3(ceil_div(W, 256), H), dim3(256), 0, s, res, hi_half, p->lo0, p->hi0, N, H, W);
+    if ((rc = fft2d_c2c(p->frame, res, N, true, s))) return rc;
+    const long long tot = (long long)N * H * W;
+    hipLaunchKernelGGL(complex_real_kernel, dim3(blocks_1d(tot)), dim3(256), 0, s, res, img, tot, 1.0f / ((float)H * (float)W));
+    return vfi::check_launch(who);
 }
 
 }  // namespace
@@ -945,43 +1030,7 @@ extern "C" int vfi_pyr_synthesize(vfi_pyr_plan *p, const float *high, const floa
                                   const int *plane_index, const float *low, unsigned long long level_mask, int flags,
                                   float *img, int N, vfi_stream_t stream) {
     VFI_REQUIRE(p && img, VFI_ERR_INVALID_ARG, "vfi_pyr_synthesize: null pointer");
-    VFI_REQUIRE(N >= 1 && N <= p->max_images, VFI_ERR_INVALID_ARG, "vfi_pyr_synthesize: N=%d (plan max %d)", N, p->max_images);
-    VFI_REQUIRE((phase && (amp || (flags & VFI_PYR_COMPLEX_COEFF))) || level_mask == 0, VFI_ERR_INVALID_ARG,
-                "vfi_pyr_synthesize: null phase/amp tables");
-    hipStream_t s = vfi::as_stream(stream);
-    const int H = p->H, W = p->W;
-    int rc;
-    // coarsest: res = FFT(low) (zeros when low is NULL)
-    float2 *res = p->lod[p->nlev & 1];
-    {
-        const long long tot = (long long)N * p->low.h * p->low.w;
-        hipLaunchKernelGGL(real_to_complex_kernel, dim3(blocks_1d(tot)), dim3(256), 0, s, low, res, tot);
-        if (low && (rc = fft2d_c2c(p->low, res, N, false, s))) return rc;
-    }
-    for (int k = p->nlev - 1; k >= 0; --k) {
-        const Size2D &next = k + 1 < p->nlev ? p->lev[k + 1] : p->low;
-        float2 *cur = p->lod[k & 1];
-        if (!((level_mask >> k) & 1ull)) {
-            syn_embed(p, k, N, res, next.h, next.w, cur, s);
-        } else {
-            VFI_REQUIRE(phase[k] && ((flags & VFI_PYR_COMPLEX_COEFF) || amp[k]), VFI_ERR_INVALID_ARG,
-                        "vfi_pyr_synthesize: null input for level %d", k);
-            if ((rc = syn_rows(p, k, N, phase[k], amp ? amp[k] : nullptr, make_map(plane_index, k, N, p->nbands, flags), s)) ||
-                (rc = syn_cols(p, k, N, res, next.h, next.w, cur, s)))
-                return rc;
-        }
-        res = cur;
-    }
-    const float2 *hi_half = nullptr;
-    if (high) {
-        if ((rc = fft2d_r2c(p, high, p->half0, N, s))) return rc;
-        hi_half = p->half0;
-    }
-    hipLaunchKernelGGL(pyr_final_kernel, dim3(ceil_div(W, 256), H), dim3(256), 0, s, res, hi_half, p->lo0, p->hi0, N, H, W);
-    if ((rc = fft2d_c2c(p->frame, res, N, true, s))) return rc;
-    const long long tot = (long long)N * H * W;
-    hipLaunchKernelGGL(complex_real_kernel, dim3(blocks_1d(tot)), dim3(256), 0, s, res, img, tot, 1.0f / ((float)H * (float)W));
-    return vfi::check_launch("vfi_pyr_synthesize");
+    return pyr_synthesize_impl(p, SynthCall{high, phase, amp, plane_index, low, level_mask, flags}, img, N, "vfi_pyr_synthesize", stream);
 }
 
 extern "C" int vfi_pyr_synthesize_backward(vfi_pyr_plan *p, const float *grad_img, int N, const float *const *phase,
@@ -995,4 +1044,19 @@ extern "C" int vfi_pyr_synthesize_backward(vfi_pyr_plan *p, const float *grad_im
     AnalyzeCall c{grad_high, grad_phase, grad_amp, plane_index, grad_low, 1.0f, level_mask, flags};
     c.adjoint = true; c.fphase = phase; c.famp = amp;
     return pyr_analyze_impl(p, grad_img, N, c, stream);
+}
+
+extern "C" int vfi_pyr_analyze_backward(vfi_pyr_plan *p, const float *grad_high, const float *const *grad_phase,
+                                        const float *const *grad_amp, const float *const *phase, const float *const *amp,
+                                        const int *plane_index, const float *grad_low, float phase_scale,
+                                        unsigned long long level_mask, int flags, float *grad_img, int N, vfi_stream_t stream) {
+    VFI_REQUIRE(p && grad_img, VFI_ERR_INVALID_ARG, "vfi_pyr_analyze_backward: null pointer");
+    VFI_REQUIRE(p->analysis_adjoint, VFI_ERR_INVALID_ARG, "vfi_pyr_analyze_backward: call vfi_pyr_plan_prepare_analysis_adjoint first");
+    const bool polar = !(flags & VFI_PYR_COMPLEX_COEFF);
+    VFI_REQUIRE(!polar || level_mask == 0 || (phase && amp), VFI_ERR_INVALID_ARG, "vfi_pyr_analyze_backward: null forward phase/amp tables");
+    VFI_REQUIRE(!polar || (phase_scale != 0.0f && phase_scale == phase_scale), VFI_ERR_INVALID_ARG, "vfi_pyr_analyze_backward: phase_scale %g",
+                (double)phase_scale);
+    SynthCall c{grad_high, grad_phase, grad_amp, plane_index, grad_low, level_mask, flags};
+    c.adjoint = true; c.fphase = phase; c.famp = amp; c.phase_scale = phase_scale;
+    return pyr_synthesize_impl(p, c, grad_img, N, "vfi_pyr_analyze_backward", stream);
 }

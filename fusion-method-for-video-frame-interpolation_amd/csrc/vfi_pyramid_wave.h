@@ -37,6 +37,7 @@ struct RowsArgs {
 };
 
 // synthesis adjoint rows (vfi_pyr_synthesize_backward): `phase` / `amp` receive d phase / d amplitude; inv_hw = 1 / (H W)
+// analysis adjoint rows (vfi_pyr_analyze_backward): `phase` / `amp` hold d phase / d amplitude; phase_scale = s, inv_hw = 1 / s
 struct RowsGradArgs : RowsArgs {
     const float *fphase, *famp;   // the forward's (phase, amplitude) planes, same layout (PlaneMap)
 };
@@ -91,6 +92,7 @@ int syn_twiddles(int M, float2 *out, int cap);      // synthesis column pass (sa
 int launch_rows_polar(const RowsArgs &a, hipStream_t s);        // analysis rows  (coeff_to_values, src/train/pyramid.py:63-69)
 int launch_rows_from_polar(const RowsArgs &a, hipStream_t s);   // synthesis rows (values_to_coeff, src/train/pyramid.py:99-107)
 int launch_rows_polar_grad(const RowsGradArgs &a, hipStream_t s);   // synthesis adjoint rows (vfi_pyrw_rows_grad.hip)
+int launch_rows_from_polar_grad(const RowsGradArgs &a, hipStream_t s);   // analysis adjoint rows (vfi_pyrw_rows_syn_grad.hip)
 int launch_ana_cols(const AnaColsArgs &a, hipStream_t s);
 int launch_syn_cols(const SynColsArgs &a, hipStream_t s);
 // supported (load, store, direction): (real, half, forward) = R2C rows, (half, real, inverse) = C2R rows, (complex, complex, *)

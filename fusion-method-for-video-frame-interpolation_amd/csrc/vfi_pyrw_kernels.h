@@ -239,8 +239,12 @@ __global__ __launch_bounds__(C::TEAM > 64 ? C::TEAM : kMaxThreads, 2) void rows_
     }
 }
 
-template <class C, bool BLU>
-__global__ __launch_bounds__(C::TEAM > 64 ? C::TEAM : kMaxThreads, 2) void rows_from_polar_kernel(const RowsArgs a) {
+// GRAD (vfi_pyr_analyze_backward): the rows are the analysis' adjoint applied to the gradients of (phase, amplitude), and the
+// prologue forms the coefficient gradient G = (d A + i s d p / A) e^{i p / s} from them and the forward's (p, A), read at the
+// same offsets (a.phase / a.amp hold d p / d A, a.phase_scale = s, a.inv_hw = 1 / s); the d p term is dropped where A == 0.
+// The synthesis instantiations (GRAD = false) compile as before.
+template <class C, bool BLU, bool GRAD = false>
+__global__ __launch_bounds__(C::TEAM > 64 ? C::TEAM : kMaxThreads, 2) void rows_from_polar_kernel(const std::conditional_t<GRAD, RowsGradArgs, RowsArgs> a) {
     using I = Io<C>;
     extern __shared__ float2 lds[];
     const int lane = threadIdx.x % C::TEAM, wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x / C::TEAM)), nw = blockDim.x / C::TEAM;   // (wave = index of this lane's team)
@@ -252,7 +256,34 @@ __global__ __launch_bounds__(C::TEAM > 64 ? C::TEAM : kMaxThreads, 2) void rows_
         const int plane = b / ngrp, y0 = (b - plane * ngrp) * C::L, img = plane / kBands, band = plane - img * kBands;
         const size_t ibase = ((size_t)(m.ints[img] + band * a.pm.band_stride) * h + y0) * n;
         float2 v[C::E];
-        if (a.pm.complex_coeff) {
+        if constexpr (GRAD) {
+            const rsrc_t rP = rsrc_of(a.phase + ibase), rA = rsrc_of(a.amp + ibase);
+            const rsrc_t rFP = rsrc_of(a.fphase + ibase), rFA = rsrc_of(a.famp + ibase);
+            const float to_rev = a.inv_hw * 0.15915494309189535f;
+#pragma unroll
+            for (int q = 0; q < I::Q0; ++q) {
+                int l, i;
+                bool ok;
+                lane_index<C, 0>(lane, q, l, i, ok);
+                ok = ok && y0 + l < h;
+                const unsigned vo = ok ? (unsigned)(l * n + i) * 4u : kOob;
+#pragma unroll
+                for (int r = 0; r < I::R0; ++r) {
+                    if (BLU && r >= I::R0_BLU) { v[q * I::R0 + r] = make_float2(0.0f, 0.0f); continue; }
+                    const int pos = i + r * I::T0;
+                    const unsigned ve = BLU && pos >= n ? kOob : vo;          // (positions past the row read 0: G = 0)
+                    // sin / cos of p / s as the synthesis prologue below evaluates them (reduced to [-0.5, 0.5] revolutions)
+                    float rev = ld1(rFP, ve, r * I::T0 * 4) * to_rev;
+                    rev -= rintf(rev);
+                    const float sn = __builtin_amdgcn_sinf(rev), cs = __builtin_amdgcn_cosf(rev);
+                    const float am = ld1(rFA, ve, r * I::T0 * 4), dp = ld1(rP, ve, r * I::T0 * 4), da = ld1(rA, ve, r * I::T0 * 4);
+                    const float t = am > 0.0f ? a.phase_scale * dp / am : 0.0f;
+                    const float2 x = fft::load_value<false>(make_float2(da * cs - t * sn, da * sn + t * cs),
+                                                            BLU ? m.ch[pos] : make_float2(0.0f, 0.0f), BLU);
+                    v[q * I::R0 + r] = (!BLU || pos < n) ? x : make_float2(0.0f, 0.0f);
+                }
+            }
+        } else if (a.pm.complex_coeff) {
             const rsrc_t rC = rsrc_of(reinterpret_cast<const float2 *>(a.phase) + ibase);
 #pragma unroll
             for (int q = 0; q < I::Q0; ++q) {

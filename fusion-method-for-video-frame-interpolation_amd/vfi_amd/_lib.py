@@ -68,6 +68,9 @@ SIGNATURES = {
     "vfi_pyr_plan_prepare_adjoint": [ctypes.c_void_p],
     "vfi_pyr_synthesize_backward": [ctypes.c_void_p, c_f, c_i, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                     ctypes.c_ulonglong, c_i, c_f, ctypes.c_void_p, ctypes.c_void_p, c_f, c_s],
+    "vfi_pyr_plan_prepare_analysis_adjoint": [ctypes.c_void_p],
+    "vfi_pyr_analyze_backward": [ctypes.c_void_p, c_f, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                 ctypes.c_void_p, c_f, c_fl, ctypes.c_ulonglong, c_i, c_f, c_i, c_s],
     "vfi_conv2d_backward_weight_workspace_floats": [c_i] * 3,
     "vfi_conv2d_backward_weight": [c_f, c_l, c_f, c_l, c_f, c_f] + [c_i] * 7 + [c_f, c_l, c_s],
     "vfi_conv2d_backward_data_workspace_floats": [c_i] * 7,

@@ -8,6 +8,8 @@ engines -- no FFT library is linked --, workspace).
 
 `reconstruct` (and `vfi_amd.train.Pyramid.inv_filter`) is differentiable with respect to its inputs: when grad mode is on
 and an input requires grad it runs as the autograd node `Synthesis`, whose backward is vfi_pyr_synthesize_backward.
+`build` (and `vfi_amd.train.Pyramid.filter` in the per-image layout) is differentiable with respect to the image in the same
+way: the autograd node `Analysis`, whose backward is vfi_pyr_analyze_backward.
 """
 import ctypes
 
@@ -126,6 +128,27 @@ class Plan:
                   work=("byte", self._bytes(n, mask, torch.is_tensor(grad_high), torch.is_tensor(grad_low)) + reads,
                         "pyr_synthesize_backward"))
 
+    def analyze_backward(self, grad_high, grad_phase, grad_amp, phase, amp, table, grad_low, phase_scale, mask, flags, grad_img):
+        """Gradient of `analyze` with respect to img, written to grad_img (N,H,W): arguments in analyze's layout; phase / amp
+        are the forward's outputs; grad_phase holds interleaved (re, im) coefficient gradients with COMPLEX_COEFF (phase, amp,
+        grad_amp unused).  grad_high / grad_low None and clear mask bits are zero gradients.  Builds the plan's
+        analysis-adjoint tables on first use."""
+        if not getattr(self, "_analysis_adjoint", False):
+            with torch.cuda.device(self.device):
+                _lib.call("vfi_pyr_plan_prepare_analysis_adjoint", self._h)
+            self._analysis_adjoint = True
+        n = grad_img.shape[0]
+        tab = (ctypes.c_int * len(table))(*table) if table is not None else None
+        polar = not flags & COMPLEX_COEFF
+        reads = 4.0 * n * sum(2 * self.nbands * a * b for k, (a, b) in enumerate(self.sizes[:-1]) if (mask >> k) & 1) if polar else 0.0
+        opt = lambda t: _ptr_array(t) if t is not None else None
+        _lib.call("vfi_pyr_analyze_backward", self._h, grad_high.data_ptr() if torch.is_tensor(grad_high) else None,
+                  _ptr_array(grad_phase), opt(grad_amp), opt(phase), opt(amp), tab,
+                  grad_low.data_ptr() if torch.is_tensor(grad_low) else None, float(phase_scale), mask, flags,
+                  _lib.dptr(grad_img, "grad_img"), n, _lib.stream_ptr(),
+                  work=("byte", self._bytes(n, mask, torch.is_tensor(grad_high), torch.is_tensor(grad_low)) + reads,
+                        "pyr_analyze_backward"))
+
     def synthesize(self, high, phase, amp, table, low, mask, flags, img):
         n = img.shape[0]
         tab = (ctypes.c_int * len(table))(*table) if table is not None else None
@@ -158,8 +181,47 @@ class Synthesis(torch.autograd.Function):
         return (None,) + tuple(ctx.layout.backward(grad.contiguous(), inputs, needs))
 
 
+class Analysis(torch.autograd.Function):
+    """The pyramid's analysis as an autograd node.  `layout` maps the library's arguments to flat outputs:
+    layout.forward(img) -> tuple of output tensors, layout.saved(outputs) -> the ones the backward reads,
+    layout.backward(saved, grads) -> gradient image, where grads holds one gradient per output, None for an output that the
+    loss does not depend on (that output's level is then dropped from the backward's level mask)."""
+
+    @staticmethod
+    def forward(ctx, layout, img):
+        outputs = layout.forward(img)
+        ctx.layout = layout
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(*layout.saved(outputs))
+        return outputs
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, *grads):
+        return None, ctx.layout.backward(ctx.saved_tensors, [g.contiguous() if g is not None else None for g in grads])
+
+
+class BandFilter(torch.autograd.Function):
+    """Plan.band_filter / band_filter_pair as autograd nodes.  The gain G is real and even, so real(ifft2(fft2(x) * G)) is
+    self-adjoint: the gradient of each image set is the same filter id applied to the output's gradient."""
+
+    @staticmethod
+    def forward(ctx, plan, specs, *imgs):
+        ctx.plan, ctx.specs = plan, specs
+        if len(imgs) == 1:
+            return plan.band_filter(imgs[0], *specs[0])
+        return plan.band_filter_pair(imgs[0], specs[0], imgs[1], specs[1])
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad):
+        grad = grad.contiguous()
+        return (None, None) + tuple(ctx.plan.band_filter(grad, *spec) if need else None
+                                    for spec, need in zip(ctx.specs, ctx.needs_input_grad[2:]))
+
+
 def wants_grad(inputs):
-    """Whether a synthesis over `inputs` has to be recorded for autograd."""
+    """Whether a transform over `inputs` has to be recorded for autograd."""
     return torch.is_grad_enabled() and any(torch.is_tensor(t) and t.requires_grad for t in inputs)
 
 
@@ -198,6 +260,35 @@ class _ComplexLayout:
         return out + [gl]
 
 
+class _ComplexAnalysisLayout:
+    """build's outputs, flattened: hi (N,H,W), nlev x band coefficients (nb,N,h,w,2) finest first, lo (N,hL,wL)."""
+
+    def __init__(self, plan, nlev, nb):
+        self.plan, self.nlev, self.nb = plan, nlev, nb
+
+    def forward(self, img):
+        plan, nlev, nb = self.plan, self.nlev, self.nb
+        n, h, w = img.shape
+        self.n = n                      # (one layout per call of build)
+        new = lambda *s: torch.empty(s, dtype=torch.float32, device=img.device)
+        bands = [new(nb, n, *plan.sizes[k], 2) for k in range(nlev)]
+        hi, lo = new(n, h, w), new(n, *plan.sizes[nlev])
+        plan.analyze(img, hi, bands, None, None, lo, 1.0, (1 << nlev) - 1, BAND_MAJOR | COMPLEX_COEFF)
+        return (hi, *bands, lo)
+
+    def saved(self, outputs):
+        return ()
+
+    def backward(self, saved, grads):
+        plan, nlev = self.plan, self.nlev
+        ref = next(g for g in grads if g is not None)
+        mask = sum(1 << k for k in range(nlev) if grads[1 + k] is not None)
+        grad_img = torch.empty((self.n, plan.h, plan.w), dtype=torch.float32, device=ref.device)
+        plan.analyze_backward(grads[0], list(grads[1:1 + nlev]), None, None, None, None, grads[-1], 1.0, mask,
+                              BAND_MAJOR | COMPLEX_COEFF, grad_img)
+        return grad_img
+
+
 class SCFpyr_PyTorch(object):
     def __init__(self, height=5, nbands=4, scale_factor=2, device=None):
         self.height = height
@@ -221,10 +312,8 @@ class SCFpyr_PyTorch(object):
         n, h, w = img.shape
         plan = self.plan(h, w, n)
         nlev, nb = self.height - 2, self.nbands
-        new = lambda *s: torch.empty(s, dtype=torch.float32, device=img.device)
-        bands = [new(nb, n, *plan.sizes[k], 2) for k in range(nlev)]
-        hi, lo = new(n, h, w), new(n, *plan.sizes[nlev])
-        plan.analyze(img, hi, bands, None, None, lo, 1.0, (1 << nlev) - 1, BAND_MAJOR | COMPLEX_COEFF)
+        layout = _ComplexAnalysisLayout(plan, nlev, nb)
+        hi, *bands, lo = Analysis.apply(layout, img) if wants_grad([img]) else layout.forward(img)
         return [hi] + [[b[i] for i in range(nb)] for b in bands] + [lo]
 
     def reconstruct(self, coeff):

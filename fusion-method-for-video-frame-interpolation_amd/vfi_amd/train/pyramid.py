@@ -17,6 +17,9 @@ Extensions used by this package's own per-frame driver (not in the reference sur
 `inv_filter` is differentiable with respect to high_level, phase, amplitude and low_level (the reference's PhaseNet
 training backpropagates its L1 term through it, src/phase_net/architecture.py:69, src/train/loss.py:5-25): with grad mode
 on and an input that requires grad it runs as the autograd node `Synthesis` (vfi_pyr_synthesize_backward).
+`filter` in the per-image layout is differentiable with respect to img in the same way (the autograd node `Analysis`,
+vfi_pyr_analyze_backward), so a loss in the pyramid domain (src/train/loss.py:5-25) can sit on a predicted image; so are
+`band_filter` / `band_filter_pair` (self-adjoint radial filters: the backward is the same filter applied to the gradient).
 """
 import ctypes
 import math
@@ -25,7 +28,7 @@ import torch
 
 from .. import _lib
 from .._lib import VfiLibraryError
-from ..steerable.SCFpyr_PyTorch import SCFpyr_PyTorch, Synthesis, wants_grad
+from ..steerable.SCFpyr_PyTorch import Analysis, BandFilter, SCFpyr_PyTorch, Synthesis, wants_grad
 from ..values import DecompValues
 
 __all__ = ["DecompValues", "Pyramid"]
@@ -55,7 +58,12 @@ class Pyramid:
 
         concat_frames=F (N = F*C images ordered frame-major): PhaseNet layout instead -- phase/amplitude[k]
         are (C, F*nbands, h, w) views (channels [f0 b0..b3, f1 b0..b3]) of block-input buffers, lists ordered
-        COARSEST first, high (C,F,H,W), low (C,F,hL,wL); see PhaseNet.normalize_vals."""
+        COARSEST first, high (C,F,H,W), low (C,F,hL,wL); see PhaseNet.normalize_vals.
+
+        The per-image layout is differentiable with respect to img (autograd node `Analysis`; the gradient of the phase is
+        dropped where the amplitude is exactly 0, where torch.atan2 would give NaN).  The concat_frames layout is not:
+        PhaseNet's inputs never need a gradient, and its outputs (the block-input buffers and amp_max included) are
+        non-differentiable -- they never carry a grad_fn, whatever img requires."""
         if img.dim() != 3:
             raise VfiLibraryError("Pyramid.filter expects (N,H,W)")
         img = img.contiguous()
@@ -66,12 +74,8 @@ class Pyramid:
         mask = (1 << nlev) - 1 if level_mask is None else int(level_mask)
         new = lambda *s: torch.empty(s, dtype=torch.float32, device=img.device)
         if concat_frames is None:
-            phase = [new(n * nb, 1, *sizes[k]) if (mask >> k) & 1 else 0 for k in range(nlev)]
-            amp = [new(n * nb, 1, *sizes[k]) if (mask >> k) & 1 else 0 for k in range(nlev)]
-            high = new(n, 1, h, w) if want_high else 0
-            low = new(n, 1, *sizes[nlev]) if want_low else 0
-            plan.analyze(img, high, phase, amp, None, low, phase_scale, mask, 0)
-            return DecompValues(high, phase, amp, low)
+            layout = _PolarAnalysisLayout(plan, nlev, nb, phase_scale, mask, want_high, want_low)
+            return layout.values(Analysis.apply(layout, img) if wants_grad([img]) else layout.forward(img))
         f = int(concat_frames)
         c = n // f
         if c * f != n:
@@ -111,7 +115,10 @@ class Pyramid:
         values): a single radial frequency-domain gain (see vfi_pyr_plan_prepare_filter).  img (N,H,W)."""
         img = img.contiguous()
         n, h, w = img.shape
-        return self.pyr.plan(h, w, n).band_filter(img, level_mask, keep_high, keep_low)
+        plan = self.pyr.plan(h, w, n)
+        if wants_grad([img]):
+            return BandFilter.apply(plan, ((level_mask, keep_high, keep_low),), img)
+        return plan.band_filter(img, level_mask, keep_high, keep_low)
 
     def band_filter_pair(self, img_a, spec_a, img_b, spec_b):
         """band_filter(img_a, **spec_a) + band_filter(img_b, **spec_b) (the sum of two unmodified level subsets of two
@@ -122,7 +129,10 @@ class Pyramid:
             raise VfiLibraryError("band_filter_pair: shape mismatch")
         n, h, w = img_a.shape
         tup = lambda d: (d["level_mask"], d.get("keep_high", False), d.get("keep_low", False))
-        return self.pyr.plan(h, w, 2 * n).band_filter_pair(img_a, tup(spec_a), img_b, tup(spec_b))
+        plan = self.pyr.plan(h, w, 2 * n)
+        if wants_grad([img_a, img_b]):
+            return BandFilter.apply(plan, (tup(spec_a), tup(spec_b)), img_a, img_b)
+        return plan.band_filter_pair(img_a, tup(spec_a), img_b, tup(spec_b))
 
     # -- synthesis -------------------------------------------------------------------------------------
     def inv_filter(self, vals):
@@ -150,6 +160,63 @@ class Pyramid:
     def set_full_size(self, h, w):
         """Only needed to invert values whose high_level was dropped (no tensor carries H, W)."""
         self._full_size = (h, w)
+
+
+class _PolarAnalysisLayout:
+    """filter's outputs in the per-image layout, flattened: [high (N,1,H,W)], phase[k], amplitude[k] ((N*nb,1,h,w)) of the
+    levels in level_mask, finest first, [low (N,1,hL,wL)]."""
+
+    def __init__(self, plan, nlev, nb, phase_scale, mask, want_high, want_low):
+        self.plan, self.nlev, self.nb, self.phase_scale, self.mask = plan, nlev, nb, phase_scale, mask
+        self.want_high, self.want_low = bool(want_high), bool(want_low)
+        self.levels = [k for k in range(nlev) if (mask >> k) & 1]
+
+    def forward(self, img):
+        plan, nb, sizes = self.plan, self.nb, self.plan.sizes
+        n, h, w = img.shape
+        self.n = n                      # (one layout per call of filter)
+        new = lambda *s: torch.empty(s, dtype=torch.float32, device=img.device)
+        phase = [new(n * nb, 1, *sizes[k]) if (self.mask >> k) & 1 else 0 for k in range(self.nlev)]
+        amp = [new(n * nb, 1, *sizes[k]) if (self.mask >> k) & 1 else 0 for k in range(self.nlev)]
+        high = new(n, 1, h, w) if self.want_high else 0
+        low = new(n, 1, *sizes[self.nlev]) if self.want_low else 0
+        plan.analyze(img, high, phase, amp, None, low, self.phase_scale, self.mask, 0)
+        return tuple([high] * self.want_high + [phase[k] for k in self.levels] + [amp[k] for k in self.levels] + [low] * self.want_low)
+
+    def _split(self, flat):
+        flat, m = list(flat), len(self.levels)
+        high = flat.pop(0) if self.want_high else None
+        low = flat.pop() if self.want_low else None
+        return high, flat[:m], flat[m:2 * m], low
+
+    def values(self, outputs):
+        high, ph, am, low = self._split(outputs)
+        phase, amp = [0] * self.nlev, [0] * self.nlev
+        for i, k in enumerate(self.levels):
+            phase[k], amp[k] = ph[i], am[i]
+        return DecompValues(high if self.want_high else 0, phase, amp, low if self.want_low else 0)
+
+    def saved(self, outputs):
+        _, ph, am, _ = self._split(outputs)
+        return (*ph, *am)
+
+    def backward(self, saved, grads):
+        plan, m = self.plan, len(self.levels)
+        gh, gp, ga, gl = self._split(grads)
+        ref = next(g for g in grads if g is not None)
+        mask = 0
+        dphi, damp, phase, amp = ([None] * self.nlev for _ in range(4))
+        for i, k in enumerate(self.levels):
+            if gp[i] is None and ga[i] is None:
+                continue
+            mask |= 1 << k
+            phase[k], amp[k] = saved[i], saved[m + i]
+            dphi[k] = gp[i] if gp[i] is not None else torch.zeros_like(phase[k])
+            damp[k] = ga[i] if ga[i] is not None else torch.zeros_like(amp[k])
+        grad_img = torch.empty((self.n, plan.h, plan.w), dtype=torch.float32, device=ref.device)
+        plan.analyze_backward(gh.squeeze(1) if gh is not None else None, dphi, damp, phase, amp, None,
+                              gl.squeeze(1) if gl is not None else None, self.phase_scale, mask, 0, grad_img)
+        return grad_img
 
 
 class _PolarLayout:

@@ -553,6 +553,30 @@ int vfi_pyr_synthesize_backward(vfi_pyr_plan *plan, const float *grad_img, int N
                                 float *grad_high, float *const *grad_phase, float *const *grad_amp, float *grad_low,
                                 vfi_stream_t stream);
 
+/* Gradient of vfi_pyr_analyze with respect to img, for training through Pyramid.filter / SCFpyr_PyTorch.build.  The
+ * analysis is real-linear from the image to the band coefficients z_{k,b} = 1/(h_k w_k) * unnormalised IFFT2_k(i *
+ * window_k(FFT2(img)) * P_a[k][b]), so its adjoint applied to coefficient gradients G is a synthesis:
+ *   grad img = Re unnormalised IFFT2( lo0 * R_0 + hi0 * FFT2(grad_high) / (H W) ),
+ *   R_k = embed_k(R_{k+1} * lomask_k) + sum_b (-i) * himask_k * (one-sided) angle mask b * FFT2_k(G_{k,b}) / (h_k w_k),
+ *   R_L = FFT2_L(grad_low) / (hL wL)
+ * -- the passes of vfi_pyr_synthesize with the tables B_k[b] = himask_k * angle mask b * H W / (h_k w_k) in place of P_s.
+ * P_a cannot be read in place there (it carries lo0 * prod_{j<k} lomask_j, which the synthesis' passes apply on the way
+ * up), so vfi_pyr_plan_prepare_analysis_adjoint builds the B_k once per plan (allocates nbands floats per band
+ * coefficient of every level; a second call is a no-op).  vfi_pyr_analyze_backward returns VFI_ERR_INVALID_ARG without them.
+ *   grad_high (N, H, W) or NULL (zeros);  grad_low (N, hL, wL) or NULL (zeros)
+ *   grad_phase[k], grad_amp[k]: gradients of vfi_pyr_analyze's phase[k], amp[k] (same layout, plane_index and flags);
+ *          phase[k], amp[k]: the forward's outputs, phase_scale the forward's.  The row pass forms
+ *          G = (d A + i * phase_scale * d p / A) * exp(i * p / phase_scale); where A == 0 the d p term is dropped (the phase
+ *          has no gradient at the origin; torch.atan2 yields NaN there).
+ *          With VFI_PYR_COMPLEX_COEFF grad_phase[k] holds G as interleaved (re, im); phase, amp, grad_amp are unused.
+ *   levels whose level_mask bit is clear contribute nothing (they only embed the coarser levels).
+ * fp32, one writer per element, no atomics: results are bit-identical from run to run. */
+int vfi_pyr_plan_prepare_analysis_adjoint(vfi_pyr_plan *plan);
+int vfi_pyr_analyze_backward(vfi_pyr_plan *plan, const float *grad_high, const float *const *grad_phase,
+                             const float *const *grad_amp, const float *const *phase, const float *const *amp,
+                             const int *plane_index, const float *grad_low, float phase_scale,
+                             unsigned long long level_mask, int flags, float *grad_img, int N, vfi_stream_t stream);
+
 /* ------------------------------------------------------------------------------------
  * Image-space stages the reference runs on the host CPU (skimage / scipy round trips)
  * ---------------------------------------------------------------------------------- */
