@@ -1,6 +1,7 @@
 // Backward of one PhaseNet level (gfx950): the HBM-bound adjoints between the existing convolution gradients
 // (vfi_conv_grad.hip).  Differentiates reference src/phase_net/phase_net.py:138-139 (bilinear resize to an arbitrary size),
-// :190-200 (ELU, tanh), :113-116 and :155-168 with reverse_normalize :80-98 (the per-level blends), and
+// :190-200 (ELU, tanh), :113-116 and :155-168 with reverse_normalize :80-98 (the per-level blends; a band level's whole
+// head in one pass), and
 // src/train/loss.py:10-20 (phase loss, L1).  Rules of sections 12 and 13: no float atomics, one writer per element,
 // reductions in an order fixed by the shape, fp32 throughout.
 #include "vfi_common.h"
@@ -189,6 +190,172 @@ __global__ void l1_backward_kernel(const float *__restrict__ a, const float *__r
     }
 }
 
+// ---- adjoint of a band level's head in one pass (vfi_phasenet_predict: 1x1 64 -> 8, tanh, emit) ---------------------
+// Per pixel gz = (emit adjoint + grad_pred_in) (1 - pred^2); grad_f[k] = sum_j W[j][k] gz[j];  grad_W[j][k] = sum gz[j] f[k],
+// grad_b[j] = sum gz[j].  A block of 256 threads walks tiles of kHeadTile pixels of one sample:
+//   A1  gz of the tile -> LDS, one (channel, pixel group) per thread;
+//   A2  one (pixel group, run of feature channels) per thread: f -> LDS (only when the parameters need a gradient),
+//       grad_f from W in LDS, stored;
+//   B   thread t owns grad_W[2w][k], grad_W[2w+1][k] (k = t % 64, w = its wave) and sums gz f over the tile's pixels
+//       in ascending order, into registers it keeps for all of the block's tiles.  grad_b rides along in every lane.
+// Pixels past the end of the sample hold zeros in LDS.  Stage 2 (head_reduce_kernel) sums the block partials in
+// block order.  The grid, the tiles of a block and both orders depend on (N, HW) alone: the bits repeat.
+// VEC = 4: 16-byte accesses (HW, every stride and every base a multiple of 4 floats); VEC = 1 otherwise.
+constexpr int kHeadTile = 128;
+constexpr int kHeadRow = kHeadTile + 4;     // floats per LDS row of f; (row / 4) odd keeps ds_read_b128 over k conflict-free
+constexpr int kHeadOut = 8 * 64 + 8;        // floats per block partial: grad_W (8, 64), grad_b (8)
+static_assert(kMaxPartials * kHeadOut <= VFI_PHASENET_HEAD_WORKSPACE_FLOATS, "head workspace");
+
+template <int VEC> struct HeadVec;
+template <> struct HeadVec<1> { typedef float type; };
+template <> struct HeadVec<4> { typedef float4 type; };
+__device__ __forceinline__ float hv_get(float v, int) { return v; }
+__device__ __forceinline__ float hv_get(const float4 &v, int i) { return i == 0 ? v.x : (i == 1 ? v.y : (i == 2 ? v.z : v.w)); }
+__device__ __forceinline__ void hv_set(float &v, int, float x) { v = x; }
+__device__ __forceinline__ void hv_set(float4 &v, int i, float x) {
+    if (i == 0) v.x = x; else if (i == 1) v.y = x; else if (i == 2) v.z = x; else v.w = x;
+}
+
+struct HeadArgs {
+    const float *f, *pred, *amp, *maxv, *w, *g_phase, *g_amp, *g_pred;
+    long long f_bs, pred_bs, amp_bs, gp_bs, gf_bs;
+    float *g_f, *part;
+    int N, HW, tiles_per_sample;
+};
+
+template <int VEC, bool WGRAD>
+__global__ __launch_bounds__(kThreads) void head_backward_kernel(HeadArgs a) {
+    typedef typename HeadVec<VEC>::type vec;
+    constexpr int PG = kHeadTile / VEC;         // pixel groups per tile
+    constexpr int KPT = 64 / (kThreads / PG);   // feature channels per thread in A2
+    __shared__ __attribute__((aligned(16))) float s_f[WGRAD ? 64 * kHeadRow : 4];
+    __shared__ __attribute__((aligned(16))) float s_gz[8 * kHeadTile];
+    __shared__ __attribute__((aligned(16))) float s_w[64 * 8];      // [k][j]
+    const int t = threadIdx.x;
+    for (int i = t; i < 512; i += kThreads) s_w[i] = a.w ? a.w[(i & 7) * 64 + (i >> 3)] : 0.0f;
+    float acc0 = 0.0f, acc1 = 0.0f, accb0 = 0.0f, accb1 = 0.0f;
+    const int HW = a.HW;
+    const long long tiles = (long long)a.N * a.tiles_per_sample;
+    for (long long tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
+        const int n = (int)(tile / a.tiles_per_sample);
+        const int px0 = (int)(tile - (long long)n * a.tiles_per_sample) * kHeadTile;
+        __syncthreads();        // the previous tile's B has read s_f and s_gz (first tile: s_w is written)
+        // A1
+        for (int e = t; e < 8 * PG; e += kThreads) {
+            const int j = e / PG, pg = e - j * PG, q = px0 + pg * VEC;
+            vec gz;
+            if (q < HW) {
+                const vec y = *reinterpret_cast<const vec *>(a.pred + (size_t)n * a.pred_bs + (size_t)j * HW + q);
+                vec g;
+                if (j < 4) {
+                    if (a.g_phase) {
+                        const vec gp = *reinterpret_cast<const vec *>(a.g_phase + ((size_t)n * 4 + j) * HW + q);
+#pragma unroll
+                        for (int v = 0; v < VEC; ++v) hv_set(g, v, hv_get(gp, v) * 3.14159265358979323846f);
+                    } else {
+#pragma unroll
+                        for (int v = 0; v < VEC; ++v) hv_set(g, v, 0.0f);
+                    }
+                } else {
+                    if (a.g_amp) {
+                        const float *am = a.amp + (size_t)n * a.amp_bs + q;
+                        const vec ga = *reinterpret_cast<const vec *>(a.g_amp + ((size_t)n * 4 + (j - 4)) * HW + q);
+                        const vec a1 = *reinterpret_cast<const vec *>(am + (size_t)j * HW);
+                        const vec a0 = *reinterpret_cast<const vec *>(am + (size_t)(j - 4) * HW);
+                        const float mx = a.maxv[n];
+#pragma unroll
+                        for (int v = 0; v < VEC; ++v) hv_set(g, v, hv_get(ga, v) * mx * (hv_get(a1, v) - hv_get(a0, v)) * 0.5f);
+                    } else {
+#pragma unroll
+                        for (int v = 0; v < VEC; ++v) hv_set(g, v, 0.0f);
+                    }
+                }
+                if (a.g_pred) {
+                    const vec gi = *reinterpret_cast<const vec *>(a.g_pred + (size_t)n * a.gp_bs + (size_t)j * HW + q);
+#pragma unroll
+                    for (int v = 0; v < VEC; ++v) hv_set(g, v, hv_get(g, v) + hv_get(gi, v));
+                }
+#pragma unroll
+                for (int v = 0; v < VEC; ++v) hv_set(gz, v, hv_get(g, v) * (1.0f - hv_get(y, v) * hv_get(y, v)));
+            } else {
+#pragma unroll
+                for (int v = 0; v < VEC; ++v) hv_set(gz, v, 0.0f);
+            }
+            *reinterpret_cast<vec *>(s_gz + j * kHeadTile + pg * VEC) = gz;
+        }
+        __syncthreads();
+        // A2
+        {
+            const int pg = t % PG, k0 = (t / PG) * KPT, q = px0 + pg * VEC;
+            const bool valid = q < HW;
+            vec gz[8];
+#pragma unroll
+            for (int j = 0; j < 8; ++j) gz[j] = *reinterpret_cast<const vec *>(s_gz + j * kHeadTile + pg * VEC);
+#pragma unroll 4
+            for (int kk = 0; kk < KPT; ++kk) {
+                const int k = k0 + kk;
+                if (WGRAD) {
+                    vec fv;
+#pragma unroll
+                    for (int v = 0; v < VEC; ++v) hv_set(fv, v, 0.0f);
+                    if (valid) fv = *reinterpret_cast<const vec *>(a.f + (size_t)n * a.f_bs + (size_t)k * HW + q);
+                    *reinterpret_cast<vec *>(s_f + k * kHeadRow + pg * VEC) = fv;
+                }
+                if (a.g_f && valid) {
+                    const float4 w0 = *reinterpret_cast<const float4 *>(s_w + k * 8), w1 = *reinterpret_cast<const float4 *>(s_w + k * 8 + 4);
+                    vec r;
+#pragma unroll
+                    for (int v = 0; v < VEC; ++v) {
+                        float s = w0.x * hv_get(gz[0], v);
+                        s = fmaf(w0.y, hv_get(gz[1], v), s);
+                        s = fmaf(w0.z, hv_get(gz[2], v), s);
+                        s = fmaf(w0.w, hv_get(gz[3], v), s);
+                        s = fmaf(w1.x, hv_get(gz[4], v), s);
+                        s = fmaf(w1.y, hv_get(gz[5], v), s);
+                        s = fmaf(w1.z, hv_get(gz[6], v), s);
+                        s = fmaf(w1.w, hv_get(gz[7], v), s);
+                        hv_set(r, v, s);
+                    }
+                    *reinterpret_cast<vec *>(a.g_f + (size_t)n * a.gf_bs + (size_t)k * HW + q) = r;
+                }
+            }
+        }
+        if (WGRAD) {
+            __syncthreads();
+            // B
+            const int k = t & 63, j0 = 2 * (t >> 6);
+            const float4 *fr = reinterpret_cast<const float4 *>(s_f + k * kHeadRow);
+            const float4 *g0 = reinterpret_cast<const float4 *>(s_gz + j0 * kHeadTile), *g1 = g0 + kHeadTile / 4;
+#pragma unroll 4
+            for (int p = 0; p < kHeadTile / 4; ++p) {
+                const float4 fv = fr[p], u = g0[p], v = g1[p];
+                acc0 = fmaf(u.x, fv.x, acc0); acc0 = fmaf(u.y, fv.y, acc0); acc0 = fmaf(u.z, fv.z, acc0); acc0 = fmaf(u.w, fv.w, acc0);
+                acc1 = fmaf(v.x, fv.x, acc1); acc1 = fmaf(v.y, fv.y, acc1); acc1 = fmaf(v.z, fv.z, acc1); acc1 = fmaf(v.w, fv.w, acc1);
+                accb0 += u.x; accb0 += u.y; accb0 += u.z; accb0 += u.w;
+                accb1 += v.x; accb1 += v.y; accb1 += v.z; accb1 += v.w;
+            }
+        }
+    }
+    if (WGRAD) {
+        float *out = a.part + (size_t)blockIdx.x * kHeadOut;
+        const int k = t & 63, j0 = 2 * (t >> 6);
+        out[j0 * 64 + k] = acc0;
+        out[(j0 + 1) * 64 + k] = acc1;
+        if (k == 0) { out[512 + j0] = accb0; out[512 + j0 + 1] = accb1; }
+    }
+}
+
+// stage 2 (one block): every output sums its column of the partials in block order
+__global__ __launch_bounds__(kThreads) void head_reduce_kernel(const float *__restrict__ part, int blocks, float *__restrict__ g_w,
+                                                               float *__restrict__ g_b) {
+    for (int o = threadIdx.x; o < kHeadOut; o += kThreads) {
+        float v = 0.0f;
+        for (int b = 0; b < blocks; ++b) v += part[(size_t)b * kHeadOut + o];
+        if (o < 512) { if (g_w) g_w[o] = v; }
+        else if (g_b) g_b[o - 512] = v;
+    }
+}
+
 template <int ACT>
 void launch_act_backward(bool v4, const float *g, long long g_bs, const float *y, long long y_bs, float *out, long long o_bs,
                          int N, long long count, vfi_stream_t stream) {
@@ -246,6 +413,41 @@ extern "C" int vfi_phasenet_emit_low_backward(const float *grad_low, const float
     LAUNCH_1D(emit_low_backward_kernel, (long long)N * HW, stream, grad_low, low_in, low_bstride, max_low, grad_pred,
               gp_bstride, N, HW);
     return vfi::check_launch("vfi_phasenet_emit_low_backward");
+}
+
+extern "C" int vfi_phasenet_predict_backward(const float *feat, long long feat_bstride, const float *pred, long long pred_bstride,
+                                             const float *amp_in, long long amp_bstride, const float *max_amp, const float *weight,
+                                             const float *grad_phase, const float *grad_amp, const float *grad_pred_in,
+                                             long long gpi_bstride, float *grad_feat, long long gf_bstride, float *grad_weight,
+                                             float *grad_bias, float *workspace, int N, int HW, vfi_stream_t stream) {
+    const bool wgrad = grad_weight || grad_bias;
+    VFI_REQUIRE(pred && (grad_feat || wgrad), VFI_ERR_INVALID_ARG, "vfi_phasenet_predict_backward: null pointer");
+    VFI_REQUIRE(!grad_feat || weight, VFI_ERR_INVALID_ARG, "vfi_phasenet_predict_backward: grad_feat needs the weights");
+    VFI_REQUIRE(!wgrad || (feat && workspace), VFI_ERR_INVALID_ARG, "vfi_phasenet_predict_backward: parameter gradients need feat and a workspace");
+    VFI_REQUIRE(!grad_amp || (amp_in && max_amp), VFI_ERR_INVALID_ARG, "vfi_phasenet_predict_backward: amplitudes missing");
+    VFI_REQUIRE(N > 0 && HW > 0, VFI_ERR_INVALID_ARG, "vfi_phasenet_predict_backward: bad sizes");
+    VFI_REQUIRE(64ll * HW < (1ll << 31), VFI_ERR_UNSUPPORTED, "vfi_phasenet_predict_backward: per-sample tensor too large for 32-bit pixel indices");
+    HeadArgs a{};
+    a.f = feat; a.pred = pred; a.amp = amp_in; a.maxv = max_amp; a.w = weight; a.g_phase = grad_phase; a.g_amp = grad_amp;
+    a.g_pred = grad_pred_in; a.f_bs = feat_bstride; a.pred_bs = pred_bstride; a.amp_bs = amp_bstride; a.gp_bs = gpi_bstride;
+    a.gf_bs = gf_bstride; a.g_f = grad_feat; a.part = workspace; a.N = N; a.HW = HW;
+    a.tiles_per_sample = (HW + kHeadTile - 1) / kHeadTile;
+    const long long tiles = (long long)N * a.tiles_per_sample;
+    const int blocks = (int)(tiles < kMaxPartials ? tiles : kMaxPartials);
+    const bool v4 = HW % 4 == 0 && aligned16(pred) && pred_bstride % 4 == 0 && (!wgrad || (aligned16(feat) && feat_bstride % 4 == 0)) &&
+                    (!grad_feat || (aligned16(grad_feat) && gf_bstride % 4 == 0)) && (!grad_phase || aligned16(grad_phase)) &&
+                    (!grad_amp || (aligned16(grad_amp) && aligned16(amp_in) && amp_bstride % 4 == 0)) &&
+                    (!grad_pred_in || (aligned16(grad_pred_in) && gpi_bstride % 4 == 0));
+    hipStream_t s = vfi::as_stream(stream);
+    if (wgrad) {
+        if (v4) hipLaunchKernelGGL((head_backward_kernel<4, true>), dim3(blocks), dim3(kThreads), 0, s, a);
+        else hipLaunchKernelGGL((head_backward_kernel<1, true>), dim3(blocks), dim3(kThreads), 0, s, a);
+        hipLaunchKernelGGL(head_reduce_kernel, dim3(1), dim3(kThreads), 0, s, workspace, blocks, grad_weight, grad_bias);
+    } else {
+        if (v4) hipLaunchKernelGGL((head_backward_kernel<4, false>), dim3(blocks), dim3(kThreads), 0, s, a);
+        else hipLaunchKernelGGL((head_backward_kernel<1, false>), dim3(blocks), dim3(kThreads), 0, s, a);
+    }
+    return vfi::check_launch("vfi_phasenet_predict_backward");
 }
 
 extern "C" int vfi_l1_forward(const float *a, const float *b, long long count, int wrap, float scale, float *workspace,

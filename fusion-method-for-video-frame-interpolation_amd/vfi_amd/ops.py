@@ -578,6 +578,67 @@ def phasenet_emit_backward(grad_phase, grad_amp, amp_in, max_amp):
     return out
 
 
+def phasenet_predict(feat, pc, amp_in, max_amp, pred=None):
+    """A band level's head in one call (vfi_phasenet_predict): feat (N,64,H,W), pc the PackedConv of the 64 -> 8 1x1 prediction
+    map, amp_in (N,8,H,W), max_amp (N,) -> (pred (N,8,H,W) post-tanh, phase, amp (N*4,1,H,W)).  Small or odd-sized levels run
+    vfi_conv2d + vfi_phasenet_emit inside the library."""
+    n, cin, h, w = feat.shape
+    if pc.cout != 8 or pc.ks != 1 or pc.cin != cin or tuple(amp_in.shape) != (n, 8, h, w) or max_amp.numel() != n:
+        raise VfiLibraryError("phasenet_predict: needs a 1x1 map with 8 outputs, amp_in (N,8,H,W) and max_amp (N,)")
+    if pred is None:
+        pred = new((n, 8, h, w), feat)
+    elif tuple(pred.shape) != (n, 8, h, w):
+        raise VfiLibraryError(f"phasenet_predict: pred shape {tuple(pred.shape)} != {(n, 8, h, w)}")
+    fp, fs = _slice_ptr(feat, "feat")
+    ap, as_ = _slice_ptr(amp_in, "amp_in")
+    pp, ps = _slice_ptr(pred, "pred")
+    phase, amp = new((n * 4, 1, h, w), feat), new((n * 4, 1, h, w), feat)
+    _lib.call("vfi_phasenet_predict", fp, fs, pc.packed.data_ptr(), pc.bias.data_ptr(), ap, as_, _lib.dptr(max_amp, "max_amp"),
+              pp, ps, phase.data_ptr(), amp.data_ptr(), n, cin, h, w, _lib.stream_ptr(),
+              work=_prof("byte", 4.0 * n * (cin + 8 + 8 + 8) * h * w, "phasenet_predict_kernel"))
+    return pred, phase, amp
+
+
+def phasenet_predict_backward(feat, pred, amp_in, max_amp, weight, grad_phase=None, grad_amp=None, grad_pred_in=None,
+                              need_feat=True, need_weight=True, need_bias=True, out=None):
+    """Adjoint of phasenet_predict in one pass (vfi_phasenet_predict_backward): -> (grad_feat (N,64,H,W), grad_weight
+    (8,64,1,1), grad_bias (8,)), None where not needed.  feat, pred, amp_in, grad_pred_in may be channel slices; weight is the
+    prediction map's (8,64,1,1) parameter; grad_phase / grad_amp (N*4,1,H,W) dense; a missing upstream gradient is zero.
+    `out`: where grad_feat goes (a channel slice is fine)."""
+    n, cin, h, w = feat.shape
+    if cin != 64 or tuple(pred.shape) != (n, 8, h, w) or tuple(weight.shape) != (8, 64, 1, 1):
+        raise VfiLibraryError("phasenet_predict_backward: feat (N,64,H,W), pred (N,8,H,W), weight (8,64,1,1)")
+    if not (need_feat or need_weight or need_bias):
+        raise VfiLibraryError("phasenet_predict_backward: no output asked for")
+    for g, name in ((grad_phase, "grad_phase"), (grad_amp, "grad_amp")):
+        if g is not None and g.numel() != n * 4 * h * w:
+            raise VfiLibraryError(f"phasenet_predict_backward: {name} shape mismatch")
+    if grad_pred_in is not None and tuple(grad_pred_in.shape) != (n, 8, h, w):
+        raise VfiLibraryError("phasenet_predict_backward: grad_pred_in shape mismatch")
+    if grad_amp is not None and (tuple(amp_in.shape) != (n, 8, h, w) or max_amp.numel() != n):
+        raise VfiLibraryError("phasenet_predict_backward: amp_in must be (N,8,H,W), max_amp (N,)")
+    fp, fs = _slice_ptr(feat, "feat")
+    pp, ps = _slice_ptr(pred, "pred")
+    ap, as_ = (None, 0) if grad_amp is None else _slice_ptr(amp_in, "amp_in")
+    ip, is_ = (None, 0) if grad_pred_in is None else _slice_ptr(grad_pred_in, "grad_pred_in")
+    gf = None
+    if need_feat:
+        gf = new((n, 64, h, w), feat) if out is None else out
+        if tuple(gf.shape) != (n, 64, h, w):
+            raise VfiLibraryError(f"phasenet_predict_backward: out shape {tuple(gf.shape)} != {(n, 64, h, w)}")
+    gp, gs = (None, 0) if gf is None else _slice_ptr(gf, "out")
+    gw = new((8, 64, 1, 1), feat) if need_weight else None
+    gb = new((8,), feat) if need_bias else None
+    ws = torch.empty(_lib.PHASENET_HEAD_WORKSPACE_FLOATS, dtype=torch.float32, device=feat.device) if need_weight or need_bias else None
+    planes = 8 + 64 * (need_weight or need_bias) + 64 * need_feat + 4 * (grad_phase is not None) + 12 * (grad_amp is not None) + \
+        8 * (grad_pred_in is not None)
+    _lib.call("vfi_phasenet_predict_backward", fp, fs, pp, ps, ap, as_, _lib.dptr(max_amp, "max_amp") if grad_amp is not None else None,
+              _lib.dptr(weight.detach(), "weight"), _lib.dptr(grad_phase, "grad_phase"), _lib.dptr(grad_amp, "grad_amp"), ip, is_,
+              gp, gs, _lib.dptr(gw), _lib.dptr(gb), _lib.dptr(ws), n, h * w, _lib.stream_ptr(),
+              work=_prof("byte", 4.0 * n * h * w * planes, "phasenet_predict_backward"))
+    return gf, gw, gb
+
+
 def phasenet_emit_low(pred, low_in, max_low):
     """The low level's output (vfi_phasenet_emit_low): pred (N,1,H,W), low_in (N,2,H,W) normalised, max_low (N,) -> (N,1,H,W)."""
     n, c, h, w = pred.shape

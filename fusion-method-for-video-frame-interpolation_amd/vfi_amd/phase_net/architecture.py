@@ -33,8 +33,22 @@ class PhaseNet(torch.nn.Module):
         """architecture.py:34-36 (map_location added: the reference file carries a cuda:0 storage tag)."""
         self.core.load_state_dict(torch.load(path, map_location="cpu"))
 
-    @torch.no_grad()
+    def fine_tune(self, mode=True):
+        """Fixed-statistics fine-tuning on or off (PhaseNetCore.fine_tune); off in a new module."""
+        self.core.fine_tune(mode)
+        return self
+
     def forward(self, img_batch, high_level=False, ada_pred=None, m=None):
+        """No graph is built unless fine_tune() was called, grad mode is on and a parameter of the core requires grad; then `prediction` and the
+        predicted levels of `vals_pred` carry one (fixed-statistics fine-tuning), so that
+        `get_loss(vals_pred, vals_target, prediction, target, pyr)[0].backward()` is one training step
+        (reference src/train/trainer.py:124-134).  The images themselves get no gradient."""
+        if self.core.fine_tuning and torch.is_grad_enabled() and any(p.requires_grad for p in self.core.layers.parameters()):
+            return self._forward(img_batch.detach(), high_level, ada_pred, m)
+        with torch.no_grad():
+            return self._forward(img_batch, high_level, ada_pred, m)
+
+    def _forward(self, img_batch, high_level, ada_pred, m):
         img_batch = img_batch.float()
         if m is None:                                                    # fused route (architecture.py:40-59)
             vals, bufs = self.pyr.filter(img_batch, concat_frames=self.core.num_img, phase_scale=1.0 / math.pi)

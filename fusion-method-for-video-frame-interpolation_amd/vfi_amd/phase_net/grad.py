@@ -1,11 +1,18 @@
-"""The differentiable pieces one PhaseNet level is made of: `PhaseNetBlock.forward` as an autograd
-node with a HIP backward, and differentiable wrappers of the level's resize and blends.  Each wrapper is a passthrough to
-the existing op when grad mode is off or nothing requires grad, so inference callers see the same kernels and bits.
+"""The differentiable pieces one PhaseNet level is made of (DESIGN.md sections 14 and 16): `PhaseNetBlock.forward` as an
+autograd node with a HIP backward, the block's feature part and a band level's head as nodes of their own (what the
+coarse-to-fine walk of `PhaseNet.forward` is built from), and differentiable wrappers of the level's resize and blends.
+Each wrapper is a passthrough to the existing op when grad mode is off or nothing requires grad, so inference callers see
+the same kernels and bits.
 
     f, c = blk(x)                                     # reference block.py:28-32
     x1 = torch.cat((resize_bilinear(f, size), phase, amp, resize_bilinear(c, size)), 1)      # phase_net.py:138-141
     phase_out, amp_out = blend_level(c1, amp, max_amp)                                       # phase_net.py:155-168, :80-90
     low_out = blend_low(c0, low, max_low)                                                    # phase_net.py:113-116, :96-98
+
+The walk's own pieces, one band level (phase_net.py:138-168):
+    x = level_input(f, c, phase, amp)                 # both resizes and the concatenation, written into one buffer
+    f = block_features(blk, x)                        # conv 1 + folded BN + ELU + conv 2 + ELU
+    c, phase_out, amp_out = level_head(blk, f, amp, max_amp)      # vfi_phasenet_predict / vfi_phasenet_predict_backward
 """
 import torch
 
@@ -56,21 +63,34 @@ def block_packs_transposed(blk):
 def block_launches(packs, x):
     """The block's three launches (BN folded, ELU / tanh in the epilogues, reflect padding for 3x3) -> (t, f, c), t the
     post-ELU output of conv 1."""
-    c1, c2, cp = packs
+    t, f = feature_launches(packs, x)
+    return t, f, ops.conv2d(f, packs[2], "zeros", "tanh")
+
+
+def feature_launches(packs, x):
+    """The feature part's two launches -> (t, f)."""
+    c1, c2 = packs[:2]
     mode = "reflect" if c1.ks == 3 else "zeros"
     t = ops.conv2d(x, c1, mode, "elu")
-    f = ops.conv2d(t, c2, mode, "elu")
-    c = ops.conv2d(f, cp, "zeros", "tanh")
-    return t, f, c
+    return t, ops.conv2d(t, c2, mode, "elu")
+
+
+def _check_eval(blk):
+    if blk.training:
+        raise NotImplementedError("PhaseNetBlock in training mode needs batch-statistics BatchNorm, which is not built; "
+                                  "call .eval() to fine-tune on the running statistics")
+
+
+def _feature_params(blk):
+    fm = blk.feature_map
+    return (fm[0].weight, fm[0].bias, fm[1].weight, fm[1].bias, fm[3].weight, fm[3].bias)
 
 
 def block_forward(blk, x):
     """PhaseNetBlock.forward: (f, c) = (feature_map(x), prediction_map(f)) with BN on its running statistics."""
-    if blk.training:
-        raise NotImplementedError("PhaseNetBlock in training mode needs batch-statistics BatchNorm, which is not built; "
-                                  "call .eval() to fine-tune on the running statistics")
-    fm, pm = blk.feature_map, blk.prediction_map
-    params = (fm[0].weight, fm[0].bias, fm[1].weight, fm[1].bias, fm[3].weight, fm[3].bias, pm[0].weight, pm[0].bias)
+    _check_eval(blk)
+    pm = blk.prediction_map
+    params = (*_feature_params(blk), pm[0].weight, pm[0].bias)
     if _wants_grad(x, *params):
         return _BlockFunction.apply(blk, x, *params)
     _, f, c = block_launches(block_packs(blk)["fwd"], x)
@@ -96,10 +116,7 @@ class _BlockFunction(torch.autograd.Function):
         blk, t = ctx.blk, ctx.t
         x, f, c = ctx.saved_tensors[:3]
         need = ctx.needs_input_grad             # (blk, x, w1, b1, gamma, beta, w2, b2, wp, bp)
-        fm = blk.feature_map
-        ks = fm[0].weight.shape[2]
-        mode = "reflect" if ks == 3 else "zeros"
-        pT1, pT2, pTp = block_packs_transposed(blk)
+        pTp = block_packs_transposed(blk)[2]
         grads = [None] * 8
         first = any(need[2:6])                      # conv 1 or its BatchNorm
         below = first or need[1] or need[6] or need[7]      # anything under the prediction map
@@ -116,29 +133,167 @@ class _BlockFunction(torch.autograd.Function):
         if g is None or not below:
             ctx.t = None
             return (None, None, *[gp if need[2 + j] else None for j, gp in enumerate(grads)])
-        ops.act_backward_(g, f, "elu")
-        if need[6] or need[7]:
-            grads[4], grads[5] = ops.conv2d_backward_weight(t, g, ks, mode, bias=bool(need[7]))
-        gx = None
-        if first or need[1]:
-            g_t = ops.conv2d_backward_data(g, pT2, mode)
-            ops.act_backward_(g_t, t, "elu")
-            if first:
-                g_wf, g_bf = ops.conv2d_backward_weight(x, g_t, ks, mode, bias=True)
-                # y = conv(x, w s) + (b - mean) s + beta with s = gamma / sqrt(var + eps)
-                bn = fm[1]
-                inv = 1.0 / torch.sqrt(bn.running_var + bn.eps)
-                s = bn.weight.detach() * inv
-                w, b = fm[0].weight.detach(), fm[0].bias.detach()
-                grads[0] = g_wf * s.view(-1, 1, 1, 1)
-                grads[1] = g_bf * s
-                grads[2] = ((g_wf * w).sum((1, 2, 3)) + g_bf * (b - bn.running_mean)) * inv
-                grads[3] = g_bf
-            if need[1]:
-                gx = ops.conv2d_backward_data(g_t, pT1, mode)
+        gx, grads[:6] = _features_backward(blk, x, t, f, g, need[1:8])
         grads = [gp if need[2 + j] else None for j, gp in enumerate(grads)]
         ctx.t = None
         return (None, gx, *grads)
+
+
+def _features_backward(blk, x, t, f, g, need):
+    """The walk below the head, shared by the block node and the feature node: g, the gradient of f, is the caller's own
+    tensor and is overwritten (ELU backward in place).  need = (x, w1, b1, gamma, beta, w2, b2) -> (gx, six gradients)."""
+    fm = blk.feature_map
+    ks = fm[0].weight.shape[2]
+    mode = "reflect" if ks == 3 else "zeros"
+    pT1, pT2, _ = block_packs_transposed(blk)
+    grads = [None] * 6
+    first = any(need[1:5])                      # conv 1 or its BatchNorm
+    ops.act_backward_(g, f, "elu")
+    if need[5] or need[6]:
+        grads[4], grads[5] = ops.conv2d_backward_weight(t, g, ks, mode, bias=bool(need[6]))
+    gx = None
+    if first or need[0]:
+        g_t = ops.conv2d_backward_data(g, pT2, mode)
+        ops.act_backward_(g_t, t, "elu")
+        if first:
+            g_wf, g_bf = ops.conv2d_backward_weight(x, g_t, ks, mode, bias=True)
+            # y = conv(x, w s) + (b - mean) s + beta with s = gamma / sqrt(var + eps)
+            bn = fm[1]
+            inv = 1.0 / torch.sqrt(bn.running_var + bn.eps)
+            s = bn.weight.detach() * inv
+            w, b = fm[0].weight.detach(), fm[0].bias.detach()
+            grads[0] = g_wf * s.view(-1, 1, 1, 1)
+            grads[1] = g_bf * s
+            grads[2] = ((g_wf * w).sum((1, 2, 3)) + g_bf * (b - bn.running_mean)) * inv
+            grads[3] = g_bf
+        if need[0]:
+            gx = ops.conv2d_backward_data(g_t, pT1, mode)
+    return gx, grads
+
+
+# ---- the walk's nodes: feature part, head, level input -----------------------------------------------------------------
+def block_features(blk, x):
+    """f = blk.feature_map(x) (conv 1 + BatchNorm on its running statistics + ELU + conv 2 + ELU), x in the reference's
+    channel order; an autograd node when x or a feature parameter requires grad."""
+    _check_eval(blk)
+    params = _feature_params(blk)
+    if _wants_grad(x, *params):
+        return _FeatureFunction.apply(blk, x, *params)
+    return feature_launches(block_packs(blk)["fwd"], x)[1]
+
+
+class _FeatureFunction(torch.autograd.Function):
+    """The block without its head.  Inputs: (blk, x, w1, b1, gamma, beta, w2, b2); keeps t (post-ELU conv 1) and f."""
+
+    @staticmethod
+    def forward(ctx, blk, x, *params):
+        t, f = feature_launches(block_packs(blk)["fwd"], x)
+        ctx.blk, ctx.t = blk, t
+        ctx.save_for_backward(x, f, *params)
+        return f
+
+    @staticmethod
+    def backward(ctx, g_f):
+        x, f = ctx.saved_tensors[:2]
+        need = ctx.needs_input_grad             # (blk, x, w1, b1, gamma, beta, w2, b2)
+        gx, grads = _features_backward(ctx.blk, x, ctx.t, f, g_f.contiguous().clone(), need[1:8])
+        ctx.t = None
+        return (None, gx, *[gp if need[2 + j] else None for j, gp in enumerate(grads)])
+
+
+HEAD_ONE_PASS = True        # the head's backward: vfi_phasenet_predict_backward, or the five-launch composition (section 16)
+
+
+def head_backward_composed(f, c, amp_in, max_amp, weight, g_phase, g_amp, g_c, need_feat=True, need_weight=True, need_bias=True):
+    """The head's adjoint from the entry points of section 14: emit backward, (+ g_c), tanh backward, 1x1 weight gradient,
+    1x1 data gradient.  Same contract as ops.phasenet_predict_backward."""
+    g = ops.phasenet_emit_backward(g_phase, g_amp, amp_in, max_amp) if g_phase is not None or g_amp is not None else None
+    if g is None:
+        g = g_c if g_c is not None else torch.zeros_like(c)
+    elif g_c is not None:
+        g = ops.add(g, g_c)
+    gz = ops.act_backward_(g, c, "tanh", out=torch.empty_like(c))
+    gw = gb = gf = None
+    if need_weight or need_bias:
+        gw, gb = ops.conv2d_backward_weight(f, gz, 1, "zeros", bias=bool(need_bias))
+    if need_feat:
+        gf = ops.conv2d_backward_data(gz, ops.packed_transposed(weight), "zeros")
+    return gf, (gw if need_weight else None), gb
+
+
+def level_head(blk, f, amp_in, max_amp):
+    """(c, phase_out, amp_out) of one band level from its features (phase_net.py:149-168 + reverse_normalize :80-90):
+    c = blk.prediction_map(f) (N,8,H,W), the de-normalised outputs (N*4,1,H,W).  One vfi_phasenet_predict call, as in
+    inference; an autograd node with a one-pass backward when f or the head's parameters require grad."""
+    _check_eval(blk)
+    pm = blk.prediction_map[0]
+    if _wants_grad(f, pm.weight, pm.bias):
+        return _HeadFunction.apply(blk, f, amp_in.detach(), max_amp.detach(), pm.weight, pm.bias)
+    return ops.phasenet_predict(f, block_packs(blk)["fwd"][2], amp_in, max_amp)
+
+
+class _HeadFunction(torch.autograd.Function):
+    """Inputs: (blk, f, amp_in, max_amp, wp, bp) -> (c, phase, amp).  c also feeds the next finer level, whose resize
+    adjoint arrives here as g_c."""
+
+    @staticmethod
+    def forward(ctx, blk, f, amp_in, max_amp, wp, bp):
+        c, phase, amp = ops.phasenet_predict(f, block_packs(blk)["fwd"][2], amp_in, max_amp)
+        ctx.save_for_backward(f, c, amp_in, max_amp, wp)
+        ctx.set_materialize_grads(False)
+        return c, phase, amp
+
+    @staticmethod
+    def backward(ctx, g_c, g_phase, g_amp):
+        need = ctx.needs_input_grad             # (blk, f, amp_in, max_amp, wp, bp)
+        if (g_c is None and g_phase is None and g_amp is None) or not (need[1] or need[4] or need[5]):
+            return (None,) * 6
+        f, c, amp_in, max_amp, wp = ctx.saved_tensors
+        cont = lambda g: g.contiguous() if g is not None else None
+        if HEAD_ONE_PASS:
+            gf, gw, gb = ops.phasenet_predict_backward(f, c, amp_in, max_amp, wp, cont(g_phase), cont(g_amp), cont(g_c),
+                                                       need_feat=need[1], need_weight=need[4], need_bias=need[5])
+        else:
+            gf, gw, gb = head_backward_composed(f, c, amp_in, max_amp, wp, cont(g_phase), cont(g_amp), cont(g_c),
+                                                need_feat=need[1], need_weight=need[4], need_bias=need[5])
+        return None, gf, None, None, gw, gb
+
+
+def level_input(f, c, phase, amp):
+    """A band level's block input in the reference's channel order (phase_net.py:138-141):
+    cat(resize(f), phase, amp, resize(c)) at phase's size, written into one buffer -- no separate concatenation.
+    Differentiable in f and c; phase and amp (the normalised analysis outputs) get no gradient."""
+    if _wants_grad(f, c):
+        return _LevelInput.apply(f, c, phase.detach(), amp.detach())
+    return _level_input(f, c, phase, amp)
+
+
+def _level_input(f, c, phase, amp):
+    n, cf, _, _ = f.shape
+    cc, cp, ca = c.shape[1], phase.shape[1], amp.shape[1]
+    h, w = phase.shape[2:]
+    x = ops.new((n, cf + cp + ca + cc, h, w), f)
+    ops.resize_bilinear(f, (h, w), align_corners=False, out=x[:, :cf])
+    ops.affine_slice(phase.contiguous(), x[:, cf:cf + cp])
+    ops.affine_slice(amp.contiguous(), x[:, cf + cp:cf + cp + ca])
+    ops.resize_bilinear(c, (h, w), align_corners=False, out=x[:, cf + cp + ca:])
+    return x
+
+
+class _LevelInput(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, f, c, phase, amp):
+        ctx.src = tuple(f.shape[2:])
+        ctx.split = (f.shape[1], f.shape[1] + phase.shape[1] + amp.shape[1])
+        return _level_input(f, c, phase, amp)
+
+    @staticmethod
+    def backward(ctx, g):
+        g = g.contiguous()
+        cf, c0 = ctx.split
+        gf = ops.resize_bilinear_adjoint(g[:, :cf], ctx.src) if ctx.needs_input_grad[0] else None
+        gc = ops.resize_bilinear_adjoint(g[:, c0:], ctx.src) if ctx.needs_input_grad[1] else None
+        return gf, gc, None, None
 
 
 # ---- resize and blends -----------------------------------------------------------------------------------------------

@@ -12,6 +12,10 @@ Execution on the MI355X (all arithmetic in libvfi_hip.so):
     channels, and normalize_vals writes phase/pi and amp/max straight into the last 16;
   * the per-level blend + de-normalisation (phase_net.py:155-168, :80-105) is one launch per level.
 Maxima are returned/kept per call on the module (as the reference does, phase_net.py:53,59,70).
+
+After `fine_tune()`, with grad mode on and a parameter of `layers` requiring grad, `forward` takes a second route,
+`_forward_grad`: the same walk as an autograd graph with HIP backward kernels, BatchNorm on its running statistics (DESIGN.md
+section 16).  Every other call runs the code above, unchanged.
 """
 import math
 
@@ -59,8 +63,16 @@ class PhaseNet(PackedModule):
         self.layers = torch.nn.ModuleList(blocks)
         self.max_amplitudes = None
         self.max_low_level = None
+        self.fine_tuning = False
         self.train(False)
         self.to(self.device)
+
+    def fine_tune(self, mode=True):
+        """Fixed-statistics fine-tuning on or off (off in a new module).  It is PhaseNet's counterpart of FusionNet's
+        training mode: `train(True)` would mean batch statistics, which are not built, and a new module's parameters
+        require grad, so callers that never backpropagate keep results without a grad_fn unless they ask here."""
+        self.fine_tuning = bool(mode)
+        return self
 
     # -- weights ------------------------------------------------------------------------------------
     def _build_packed(self):
@@ -143,6 +155,8 @@ class PhaseNet(PackedModule):
             m = self.pyr.height - 2
         if self.max_amplitudes is None:
             raise RuntimeError("call normalize_vals(vals) before forward(vals) (phase_net.py two-call protocol)")
+        if self.fine_tuning and torch.is_grad_enabled() and any(p.requires_grad for p in self.layers.parameters()):
+            return self._forward_grad(vals, m)
         packed = self.packed()
         low_in = vals.low_level.contiguous()
         b, _, hl, wl = low_in.shape
@@ -194,6 +208,29 @@ class PhaseNet(PackedModule):
                       x.stride(0), self.max_amplitudes[idx].data_ptr(), fp[:, 64:].data_ptr(), fp.stride(0), p_out.data_ptr(),
                       a_out.data_ptr(), b, 64, h, w, stream,
                       work=("byte", 4.0 * b * (64 + 8 + 8 + 8) * h * w, "phasenet_predict_kernel") if _lib.PROFILE is not None else None)
+            phases.append(p_out); amps.append(a_out)
+        for _ in range(self.pyr.height - 2 - m):                                           # :91-93
+            phases.append(0); amps.append(0)
+        return DecompValues(high, phases[::-1], amps[::-1], low)
+
+    def _forward_grad(self, vals, m):
+        """The same walk as a graph of the nodes of vfi_amd/phase_net/grad.py, in the reference's
+        channel order [feature | phase | amp | prediction]: fixed-statistics fine-tuning.  Taken only after fine_tune(), with grad
+        mode on and a parameter of self.layers requiring grad.  The normalised inputs and the maxima get no gradient."""
+        from . import grad as G
+        low_in = vals.low_level.detach().contiguous()
+        f, c = G.block_forward(self.layers[0], low_in)                                     # :113
+        low = G.blend_low(c, low_in, self.max_low_level)                                   # :115-116 + :96-98
+        hs = vals.high_level.shape
+        high = torch.zeros((hs[0], 1, hs[2], hs[3]), dtype=torch.float32, device=low_in.device)   # :127-128
+        phases, amps = [], []
+        for idx in range(m):
+            ph, am = vals.phase[idx].detach(), vals.amplitude[idx].detach()
+            i = idx + 1 if idx + 1 < len(self.layers) - 1 else len(self.layers) - 1        # :148
+            blk = self.layers[i]
+            x = G.level_input(f, c, ph, am)                                                # :138-141
+            f = G.block_features(blk, x)
+            c, p_out, a_out = G.level_head(blk, f, am, self.max_amplitudes[idx])           # :149-168 + :80-90
             phases.append(p_out); amps.append(a_out)
         for _ in range(self.pyr.height - 2 - m):                                           # :91-93
             phases.append(0); amps.append(0)

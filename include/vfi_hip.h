@@ -445,6 +445,26 @@ int vfi_phasenet_emit_backward(const float *grad_phase, const float *grad_amp, c
 int vfi_phasenet_emit_low_backward(const float *grad_low, const float *low_in, long long low_bstride, const float *max_low,
                                    float *grad_pred, long long gp_bstride, int N, int HW, vfi_stream_t stream);
 
+/* Adjoint of vfi_phasenet_predict (one band level's head: 1x1 64 -> 8, tanh, vfi_phasenet_emit) in one pass over the pixels.
+ * feat (N, 64, HW) and pred (N, 8, HW; the forward's post-tanh output) with batch strides, amp_in / max_amp as in the forward,
+ * weight (8, 64) the prediction map's nn.Conv2d weight as it is (not packed).  Upstream: grad_phase, grad_amp (N * 4, HW)
+ * dense, grad_pred_in (N, 8, HW) with a batch stride -- what the next finer level's resize adjoint sends back to pred; any of
+ * the three may be NULL (= zero).  Per pixel
+ *   g[0:4] = pi * grad_phase + grad_pred_in[0:4]
+ *   g[4:8] = grad_amp * max_amp[n] * (amp_in[4:8] - amp_in[0:4]) / 2 + grad_pred_in[4:8]
+ *   gz     = g * (1 - pred^2)
+ * and grad_feat[k] = sum_j weight[j][k] gz[j] (N, 64, HW; written, not accumulated), grad_weight[j][k] = sum gz[j] feat[k]
+ * (8, 64), grad_bias[j] = sum gz[j] (8), the sums over all pixels and samples.  An output that is NULL is skipped (at least
+ * one is given; feat is read only for the parameter gradients, weight only for grad_feat).  The parameter gradients are a
+ * two-stage reduction over `workspace` (VFI_PHASENET_HEAD_WORKSPACE_FLOATS; at most 1024 block partials, then one block) in an
+ * order fixed by (N, HW).  16-byte accesses when HW, every stride and every base allow, 4-byte otherwise.  64 * HW < 2^31. */
+#define VFI_PHASENET_HEAD_WORKSPACE_FLOATS (1024 * 520)
+int vfi_phasenet_predict_backward(const float *feat, long long feat_bstride, const float *pred, long long pred_bstride,
+                                  const float *amp_in, long long amp_bstride, const float *max_amp, const float *weight,
+                                  const float *grad_phase, const float *grad_amp, const float *grad_pred_in,
+                                  long long gpi_bstride, float *grad_feat, long long gf_bstride, float *grad_weight,
+                                  float *grad_bias, float *workspace, int N, int HW, vfi_stream_t stream);
+
 /* out[0] = scale / count * sum |w(a - b)| over `count` floats, w(d) = atan2(sin d, cos d) when wrap != 0, else d.
  * wrap = 0, scale = 1: nn.L1Loss (loss.py:8,20).  wrap = 1, scale = nbands, a = the target's and b = the output's phases
  * of one level: that level's term of the phase loss, the sum over the orientations of the mean |delta_psi| (loss.py:10-16).

@@ -1,0 +1,97 @@
+#!/usr/bin/env python3
+"""Cost of fine-tuning the whole PhaseNet on a 1080x1920 Lab frame pair (N = 3 colours): the inference
+forward of the coarse-to-fine walk, the same forward as an autograd graph, and the HIP backward of one full step, at full m
+and at m = 4; and the head adjoint at the finest level's shape, vfi_phasenet_predict_backward against the five-launch
+composition of the section-14 entry points.  Per-call HIP events."""
+import math
+import os
+import sys
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [ROOT, os.path.join(ROOT, "fusion-method-for-video-frame-interpolation_amd"), os.path.join(ROOT, "tests")]
+import phasenet_walk_ref as W  # noqa: E402
+from vfi_amd import ops  # noqa: E402
+from vfi_amd.phase_net import grad as G  # noqa: E402
+from vfi_amd.phase_net.core import PhaseNetCore  # noqa: E402
+from vfi_amd.train.loss import l1_loss, phase_term  # noqa: E402
+from vfi_amd.train.pyramid import Pyramid  # noqa: E402
+from vfi_amd.train.utils import calc_pyr_height  # noqa: E402
+
+
+def timed(fn, iters, warm):
+    for _ in range(warm):
+        fn()
+    torch.cuda.synchronize()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(iters):
+        fn()
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1) / iters
+
+
+def head(h, w, n=3, iters=10, warm=3):
+    dev = torch.device("cuda:0")
+    g = torch.Generator().manual_seed(0)
+    r = lambda *s: torch.randn(s, generator=g).to(dev)
+    fp = r(n, 72, h, w)
+    fp[:, 64:] = torch.tanh(fp[:, 64:])
+    f, pred, amp, mx, wp = fp[:, :64], fp[:, 64:], torch.rand((n, 8, h, w), generator=g).to(dev), torch.ones(n, device=dev), r(8, 64, 1, 1) / 8
+    gp, ga, gc = r(n * 4, 1, h, w), r(n * 4, 1, h, w), r(n, 8, h, w)
+    t_new = timed(lambda: ops.phasenet_predict_backward(f, pred, amp, mx, wp, gp, ga, gc), iters, warm)
+    t_old = timed(lambda: G.head_backward_composed(f, pred, amp, mx, wp, gp, ga, gc), iters, warm)
+    planes = 64 + 8 + 8 + 16 + 64
+    print(f"head adjoint, N={n} {h}x{w}: one pass {t_new:.3f} ms ({4e-9 * n * h * w * planes / (t_new * 1e-3):.0f} GB/s of {planes} planes), "
+          f"five-launch composition {t_old:.3f} ms, ratio {t_old / t_new:.2f}")
+
+
+def step(h, w, m, n=3, iters=3, warm=1):
+    dev = torch.device("cuda:0")
+    height = calc_pyr_height(torch.empty(1, h, w))
+    core = PhaseNetCore(height, dev).fine_tune()
+    core.load_state_dict(W.net_state(0))
+    pyr = Pyramid(height=height, nbands=4, scale_factor=W.S2, device=dev)
+    imgs = torch.rand((2 * n, h, w), generator=torch.Generator().manual_seed(1)).to(dev)
+    vals, bufs = pyr.filter(imgs, concat_frames=2, phase_scale=1.0 / math.pi)
+    nv = core.normalize_vals(vals, concat=bufs)
+    with torch.no_grad():
+        t_inf = timed(lambda: core(nv, m), iters, warm)
+        out = core(nv, m)
+    tp = [p.clone() + 0.3 if torch.is_tensor(p) else p for p in out.phase]
+    ta = [a.clone() + 0.1 if torch.is_tensor(a) else a for a in out.amplitude]
+    tl = out.low_level.clone() + 0.1
+    del out
+
+    def loss():
+        v = core(nv, m)
+        total = l1_loss(v.low_level, tl)
+        for p, a, pt, at in zip(v.phase, v.amplitude, tp, ta):
+            if torch.is_tensor(p):
+                total = total + 0.005 * phase_term(p, pt, 4) + l1_loss(a, at)
+        return total
+    t_fwd = timed(loss, iters, warm)
+
+    def full():
+        core.zero_grad(set_to_none=True)
+        loss().backward()
+    t_step = timed(full, iters, warm)
+    t_bwd = t_step - t_fwd
+    print(f"PhaseNet walk, N={n} {h}x{w}, height {height}, m = {m if m is not None else height - 2}")
+    print(f"  inference forward          {t_inf:8.3f} ms")
+    print(f"  forward as a graph + loss  {t_fwd:8.3f} ms")
+    print(f"  backward                   {t_bwd:8.3f} ms = {t_bwd / t_inf:.2f} x inference forward")
+
+
+def main():
+    head(1080, 1920)
+    torch.cuda.empty_cache()
+    for m in (None, 4):
+        step(1080, 1920, m)
+        torch.cuda.empty_cache()
+
+
+if __name__ == "__main__":
+    main()
