@@ -3,6 +3,8 @@
 #pragma once
 #include "vfi_common.h"
 
+#include <atomic>
+
 namespace vfi {
 namespace conv {
 
@@ -60,6 +62,52 @@ struct ConvArgs {
     long long pool_bs;
     int pool_max;           // 1: max pooling, 0: average
 };
+
+// F(2x2) Winograd kernel (vfi_conv_winograd.hip; declared here so that tests/native/conv_items_check.cpp can walk the
+// item order on the host).  One work item = (K split, sample, spatial tile, 32-channel block).
+namespace w2 {
+constexpr int TH = 8, TW = 32, BN = 32;      // output tile and channel block of an item (WinoTile)
+struct Item {
+    int split, n, x0, y0, nb;
+    bool valid;
+};
+
+__host__ __device__ __forceinline__ Item decode_item(const ConvArgs &a, int L) {
+    Item it;
+    const int cb = a.Cout_pad / BN;
+    it.split = fast_div(L, a.fd_items);
+    const int Lr = L - it.split * a.wino_items;
+    // XCD-aware order.  Workgroup L runs on XCD L % 8 (own L2 each).  Consecutive slots of one XCD take the channel
+    // blocks of the SAME spatial tile, then the next tile of a run of `wino_run` horizontally adjacent tiles: the input
+    // tile is fetched once for all channel blocks, and the 128-byte lines a tile shares with its left / right neighbours
+    // (a tile is exactly one line wide, its halo touches both neighbouring lines) stay inside one L2 within a run
+    // (fabric reads of the 1080p 64->64 layers: 3.4 -> 1.5 GB by FETCH_SIZE).  Runs are dealt round-robin to the XCDs.
+    // (run-time divisors through their precomputed reciprocals: the decoding runs once per item and wave, twice over)
+    const int xcd = Lr & 7, q = Lr >> 3;
+    const int tq = fast_div(q, a.fd_cb), run = a.wino_run;
+    it.nb = q - tq * cb;
+    const int tr = fast_div(tq, a.fd_run);
+    const int tl = (tr * 8 + xcd) * run + (tq - tr * run);
+    it.n = fast_div(tl, a.fd_tiles);
+    const int t = tl - it.n * a.wino_tiles;
+    it.valid = it.n < a.wino_batch;
+    const int ty = fast_div(t, a.fd_tiles_x);
+    it.x0 = (t - ty * a.tiles_x) * TW;
+    it.y0 = ty * TH;
+    return it;
+}
+}  // namespace w2
+
+// Test aid vfi_debug_conv_override (vfi_core.hip; process-global, relaxed: it affects later calls only).
+// conv_override_mode: -1 = as configured, else the value VFI_CONV_WINOGRAD4 would have (winograd4_suits).
+// conv_override_max_workgroups: 0 = no cap, else the three persistent Winograd launches use min(grid, k) workgroups --
+// the grid and nothing else: run length, K split, item count and workspace keep following the device's resident count, so
+// the output bits cannot depend on the cap.
+extern std::atomic<int> conv_override_mode, conv_override_max_workgroups;
+inline unsigned capped_grid(long long grid) {
+    const int cap = conv_override_max_workgroups.load(std::memory_order_relaxed);
+    return (unsigned)(cap > 0 && grid > cap ? cap : grid);
+}
 
 __device__ __forceinline__ float apply_act(float v, int act) {
     switch (act) {

@@ -68,37 +68,10 @@ __device__ __forceinline__ const char *uni(const char *p) {
     return reinterpret_cast<const char *>(((unsigned long long)hi << 32) | lo);
 }
 
-// One work item = (K split, sample, spatial tile, 32-channel block).
-struct Item {
-    int split, n, x0, y0, nb;
-    bool valid;
-};
-
-__device__ __forceinline__ Item decode_item(const ConvArgs &a, int L) {
-    using T = WinoTile;
-    Item it;
-    const int cb = a.Cout_pad / T::BN;
-    it.split = fast_div(L, a.fd_items);
-    const int Lr = L - it.split * a.wino_items;
-    // XCD-aware order.  Workgroup L runs on XCD L % 8 (own L2 each).  Consecutive slots of one XCD take the channel
-    // blocks of the SAME spatial tile, then the next tile of a run of `wino_run` horizontally adjacent tiles: the input
-    // tile is fetched once for all channel blocks, and the 128-byte lines a tile shares with its left / right neighbours
-    // (a tile is exactly one line wide, its halo touches both neighbouring lines) stay inside one L2 within a run
-    // (fabric reads of the 1080p 64->64 layers: 3.4 -> 1.5 GB by FETCH_SIZE).  Runs are dealt round-robin to the XCDs.
-    // (run-time divisors through their precomputed reciprocals: the decoding runs once per item and wave, twice over)
-    const int xcd = Lr & 7, q = Lr >> 3;
-    const int tq = fast_div(q, a.fd_cb), run = a.wino_run;
-    it.nb = q - tq * cb;
-    const int tr = fast_div(tq, a.fd_run);
-    const int tl = (tr * 8 + xcd) * run + (tq - tr * run);
-    it.n = fast_div(tl, a.fd_tiles);
-    const int t = tl - it.n * a.wino_tiles;
-    it.valid = it.n < a.wino_batch;
-    const int ty = fast_div(t, a.fd_tiles_x);
-    it.x0 = (t - ty * a.tiles_x) * T::TW;
-    it.y0 = ty * T::TH;
-    return it;
-}
+// One work item = (K split, sample, spatial tile, 32-channel block): vfi_conv_common.h, w2::decode_item.
+using w2::Item;
+using w2::decode_item;
+static_assert(WinoTile::TH == w2::TH && WinoTile::TW == w2::TW && WinoTile::BN == w2::BN, "the item order's tile");
 
 // RES: a residual tensor is added after the activation.  Its (ordinary) loads make the compiler drain the DMA ring
 // in every item epilogue, so layers without a residual get an instantiation without them.
@@ -518,7 +491,7 @@ int vfi::conv::launch_winograd(const ConvArgs &a, int N, hipStream_t s) {
     b.fd_tiles_x = make_fastdiv((unsigned)b.tiles_x);
     b.fd_splits = make_fastdiv((unsigned)b.splits);
     const long long items = (long long)b.wino_items * b.splits;
-    dim3 grid((unsigned)(items < resident ? items : resident));
+    dim3 grid(capped_grid(items < resident ? items : resident));
     const int act = b.splits > 1 ? 0 : b.act;      // split-K: the reduce kernel applies bias / activation / residual
     // pooled second output: in the epilogue when the layer is a plain ReLU layer in one piece, else a pass afterwards
     const bool pool_fused = b.pool && b.splits == 1 && !b.res && act == 1;

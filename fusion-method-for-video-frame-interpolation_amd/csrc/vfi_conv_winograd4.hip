@@ -377,7 +377,9 @@ bool vfi::conv::winograd4_suits(const ConvArgs &a, int N) {
     using T = Wino4Tile;
     // VFI_CONV_WINOGRAD4: 0 = never (A/B aid: the F(2x2) kernel takes everything), 2 = every plain layer whatever its size
     // (fuzzing small shapes through this kernel); default 1
-    static const int mode = getenv("VFI_CONV_WINOGRAD4") ? atoi(getenv("VFI_CONV_WINOGRAD4")) : 1;
+    static const int configured = getenv("VFI_CONV_WINOGRAD4") ? atoi(getenv("VFI_CONV_WINOGRAD4")) : 1;
+    const int forced = conv_override_mode.load(std::memory_order_relaxed);      // (vfi_debug_conv_override: -1 unless a test set it)
+    const int mode = forced >= 0 ? forced : configured;
     if (!mode) return false;
     if (a.pool && (a.res || a.act != 1)) return false;          // pooled output: plain ReLU layers only (as the F(2x2) kernel fuses it)
     const long long items = (long long)vfi::ceil_div(a.W, T::TW) * vfi::ceil_div(a.H, T::TH) * N * (a.Cout_pad / T::BN);
@@ -448,7 +450,7 @@ int vfi::conv::launch_winograd4(const ConvArgs &a, int N, hipStream_t s) {
     b.fd_tiles_x = make_fastdiv((unsigned)b.tiles_x);
     b.fd_splits = make_fastdiv(1u);
     if (winograd4m_enabled()) return launch_winograd4m(b, s);
-    dim3 grid((unsigned)(b.wino_items < resident ? b.wino_items : resident));
+    dim3 grid(capped_grid(b.wino_items < resident ? b.wino_items : resident));
     if (b.pool) hipLaunchKernelGGL((conv3x3_winograd4_kernel<1, false, true>), grid, dim3(T::THREADS), T::LDS_BYTES, s, b);
     else if (b.res) hipLaunchKernelGGL((conv3x3_winograd4_kernel<-1, true>), grid, dim3(T::THREADS), T::LDS_BYTES, s, b);
     else if (b.act == 0) hipLaunchKernelGGL((conv3x3_winograd4_kernel<0>), grid, dim3(T::THREADS), T::LDS_BYTES, s, b);

@@ -52,8 +52,9 @@ struct Item {
     bool valid;
 };
 
-// Same XCD-aware item order as the F(2x2) kernel (vfi_conv_winograd.hip: decode_item), one K split.
-__device__ __forceinline__ Item decode_item(const ConvArgs &a, int L) {
+// Same XCD-aware item order as the F(2x2) kernel (vfi_conv_common.h: w2::decode_item), one K split.  (Callable on the host:
+// tests/native/conv_items_check.cpp.)
+__host__ __device__ __forceinline__ Item decode_item(const ConvArgs &a, int L) {
     using T = Wino4Tile;
     Item it;
     const int cb = a.Cout_pad / T::BN;

@@ -1,5 +1,5 @@
 // Library-wide entry points: ABI version, status strings, thread-local error detail.
-#include "vfi_common.h"
+#include "vfi_conv_common.h"
 #include <cstring>
 
 namespace vfi {
@@ -38,6 +38,19 @@ extern "C" int vfi_debug_poison_lds(vfi_stream_t stream) {
     if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) cus = prop.multiProcessorCount;
     hipLaunchKernelGGL(poison_lds_kernel, dim3(4 * cus), dim3(256), kBytes, vfi::as_stream(stream), kBytes / 4);
     return vfi::check_launch("vfi_debug_poison_lds");
+}
+
+// Test aid: which F(4x4) selection rule winograd4_suits applies and how many workgroups the persistent Winograd kernels
+// are launched with (vfi_conv_common.h: capped_grid).  With few workgroups a small layer gives each of them several work
+// items, so the walk across item boundaries runs at shapes whose float64 reference costs milliseconds.
+std::atomic<int> vfi::conv::conv_override_mode{-1}, vfi::conv::conv_override_max_workgroups{0};
+
+extern "C" int vfi_debug_conv_override(int winograd4_mode, int max_workgroups) {
+    VFI_REQUIRE(winograd4_mode >= -1 && winograd4_mode <= 2, VFI_ERR_INVALID_ARG, "vfi_debug_conv_override: winograd4_mode %d", winograd4_mode);
+    VFI_REQUIRE(max_workgroups >= 0, VFI_ERR_INVALID_ARG, "vfi_debug_conv_override: max_workgroups %d", max_workgroups);
+    vfi::conv::conv_override_mode.store(winograd4_mode, std::memory_order_relaxed);
+    vfi::conv::conv_override_max_workgroups.store(max_workgroups, std::memory_order_relaxed);
+    return VFI_OK;
 }
 
 extern "C" const char *vfi_last_error(void) { return vfi::g_last_error; }

@@ -21,6 +21,7 @@ class VfiLibraryError(RuntimeError):
 # name -> argtypes.  tests/test_abi.py checks this table against include/vfi_hip.h.
 SIGNATURES = {
     "vfi_debug_poison_lds": [c_s],
+    "vfi_debug_conv_override": [c_i, c_i],
     "vfi_adacof_forward": [c_f] * 5 + [c_i] * 8 + [c_s],
     "vfi_adacof_backward": [c_f] * 8 + [c_i] * 8 + [c_s],
     "vfi_adacof_fused": [c_f] * 13 + [c_i] * 6 + [c_s],

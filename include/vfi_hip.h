@@ -56,6 +56,15 @@ const char *vfi_last_error(void);
  * start on NaN-filled LDS -- a kernel whose result depends on LDS it has not written itself then shows deterministically
  * (tests/test_pyramid_gpu.py::test_results_do_not_depend_on_stale_lds). */
 int vfi_debug_poison_lds(vfi_stream_t stream);
+/* Test aid (no reference counterpart), process-global, affects later calls only (tests/test_conv_walk_gpu.py).
+ *   winograd4_mode  -1: as configured (VFI_CONV_WINOGRAD4 or the default); 0, 1, 2: as that variable -- 0 = every 3x3
+ *                   layer on the F(2x2) Winograd kernel, 1 = the cost model, 2 = every eligible layer on the F(4x4) kernels.
+ *                   vfi_conv2d_algo answers accordingly.
+ *   max_workgroups  0: no cap; k >= 1: the persistent Winograd kernels are launched with min(grid, k) workgroups, so that a
+ *                   small layer gives every workgroup several work items.  Only the launch grid changes -- K split, item
+ *                   order and workspace use do not -- so the output bits do not depend on it.
+ * Anything else is VFI_ERR_INVALID_ARG and changes nothing.  (-1, 0) restores the library's own behaviour. */
+int vfi_debug_conv_override(int winograd4_mode, int max_workgroups);
 
 /* ------------------------------------------------------------------------------------
  * AdaCoF deformable sampling

@@ -21,6 +21,20 @@ def test_division_by_reciprocal_is_exact(tmp_path):
     assert r.returncode == 0 and " 0 wrong" in r.stdout, r.stdout[-2000:]
 
 
+@pytest.mark.skipif(not os.path.exists(HIPCC), reason="needs hipcc")
+def test_item_order_of_the_persistent_winograd_kernels(tmp_path):
+    """The decode_item functions of the F(2x2) and F(4x4) kernels, compiled for the host, over 1728 geometries (x 5 K splits
+    for F(2x2)): every (split, sample, tile, channel block) from exactly one valid item, padding items past the batch, tile
+    origins inside the grid, a tile's channel blocks in slots L, L + 8, ... (tests/native/conv_items_check.cpp)."""
+    exe = str(tmp_path / "conv_items_check")
+    subprocess.check_call([HIPCC, "--cuda-host-only", "-O2", "-std=c++17",
+                           "-I", os.path.join(ROOT, "fusion-method-for-video-frame-interpolation_amd", "csrc"),
+                           "-I", os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "native", "conv_items_check.cpp"),
+                           "-o", exe])
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0 and "checked 10368 geometries, 0 violations" in r.stdout, r.stdout[-2000:]
+
+
 def test_generated_chunk_body_of_the_m32_winograd_kernel_on_the_cpu():
     """tools/gen_wino4m.py emits the hand-scheduled chunk body of conv3x3_winograd4m_kernel; tools/sim_wino4m.py interprets
     that text for one wave on the CPU (64 lanes; an LDS read only delivers at the `s_waitcnt lgkmcnt` that retires it, so

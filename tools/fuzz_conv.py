@@ -8,7 +8,7 @@ sys.path[:0] = [ROOT, os.path.join(ROOT, "fusion-method-for-video-frame-interpol
 from vfi_amd import ops
 dev = torch.device("cuda:0")
 rnd = random.Random(int(sys.argv[1]) if len(sys.argv) > 1 else 0)
-worst = 0.0
+worst, fails = 0.0, 0
 for it in range(int(sys.argv[2]) if len(sys.argv) > 2 else 150):
     n, cin, cout = rnd.randint(1, 3), rnd.randint(1, 70), rnd.randint(1, 70)
     h, w = rnd.randint(2, 40), rnd.choice([rnd.randint(2, 40), rnd.randint(60, 140), 32, 64, 96, 128])
@@ -29,7 +29,11 @@ for it in range(int(sys.argv[2]) if len(sys.argv) > 2 else 150):
     out = ops.conv2d(x.to(dev), pc, pad, act, residual=None if res is None else res.to(dev))
     torch.cuda.synchronize()
     err = (out.cpu().double() - ref).abs().max().item()
-    worst = max(worst, err)
-    if err > 1e-4 or not torch.isfinite(out).all():
-        print("FAIL", (n, cin, cout, h, w, pad, act, use_res), err)
+    finite = bool(torch.isfinite(out).all())
+    if not finite or not err <= worst:       # (max() would drop a NaN: max(0.0, nan) is 0.0)
+        worst = err if finite else float("inf")
+    if not finite or not err <= 1e-4:
+        fails += 1
+        print("FAIL", (n, cin, cout, h, w, pad, act, use_res), err, "" if finite else "non-finite output")
 print("cases done, worst abs error", worst)
+sys.exit(1 if fails else 0)
