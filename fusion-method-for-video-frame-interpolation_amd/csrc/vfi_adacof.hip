@@ -32,7 +32,7 @@
 // writes one element of each gradient plane.  No atomics, no cross-thread reduction: deterministic.  Measured at
 // 1080x1920, F=5: 0.75 ms (1.7 TB/s effective) -- like the planar forward it is bound by the per-corner 4-B gathers
 // (L1 address / tag throughput), not by HBM: FETCH_SIZE + WRITE_SIZE come to ~1 GB per launch, ~1 TB/s.
-#include "vfi_common.h"
+#include "vfi_grad_common.h"
 
 #include <cstdlib>
 
@@ -507,8 +507,6 @@ __global__ __launch_bounds__(256) void adacof_backward_kernel(
             if (grad_offset_j) store_vec<VEC>(grad_offset_j + t, gb);
         }
 }
-
-inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
 }  // namespace
 

@@ -2,75 +2,24 @@
 // (vfi_conv_grad.hip) and the existing sampler gradient (vfi_adacof.hip).  Differentiates reference
 // src/adacof/models/adacofnet.py:13-153 (KernelEstimation: ReLU, AvgPool2d(2), Upsample(x2, bilinear, align_corners=True),
 // additive skips, softmax / sigmoid heads) and :191-217 (blend, smoothness terms), and src/adacof/utility.py:67-77
-// (Charbonnier).  Rules of section 12: no float atomics, one writer per element, reductions in an order fixed by the shape.
-#include "vfi_common.h"
-
-#include <cstdint>
+// (Charbonnier).  The rules: vfi_grad_common.h.
+#include "vfi_grad_common.h"
 
 namespace {
 
-constexpr int kThreads = 256;
-constexpr int kMaxPartials = 1024;      // blocks of a two-stage reduction (VFI_REDUCE_WORKSPACE_FLOATS = 4 * this)
-
-inline int blocks_for(long long n) {
-    long long b = (n + kThreads - 1) / kThreads;
-    return (int)(b < 1 ? 1 : (b > 8 * 2048 ? 8 * 2048 : b));  // grid-stride beyond 16k blocks
-}
-// reduction grids depend on the element count alone, so the summation order -- and the bits -- repeat
-inline int reduce_blocks(long long n) {
-    long long b = (n + kThreads - 1) / kThreads;
-    return (int)(b < 1 ? 1 : (b > kMaxPartials ? kMaxPartials : b));
-}
-__host__ __device__ inline bool aligned16(const void *p) { return ((uintptr_t)p & 15) == 0; }
-
-#define LAUNCH_1D(kernel, total, stream, ...) \
-    hipLaunchKernelGGL(kernel, dim3(blocks_for(total)), dim3(kThreads), 0, vfi::as_stream(stream), __VA_ARGS__)
-
-#define GRID_STRIDE(i, total) \
-    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < (total); i += (long long)gridDim.x * blockDim.x)
-
 // ---- elementwise glue ---------------------------------------------------------------------------------------------
-// T = float (any count) or float4 (count, strides multiples of 4, 16-byte aligned bases): `count` is in units of T.
-template <typename T> __device__ __forceinline__ T vadd(T a, T b);
-template <> __device__ __forceinline__ float vadd(float a, float b) { return a + b; }
-template <> __device__ __forceinline__ float4 vadd(float4 a, float4 b) { return make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w); }
-template <typename T> __device__ __forceinline__ T vmask(T g, T y);
-template <> __device__ __forceinline__ float vmask(float g, float y) { return y > 0.0f ? g : 0.0f; }
-template <> __device__ __forceinline__ float4 vmask(float4 g, float4 y) {
-    return make_float4(y.x > 0.0f ? g.x : 0.0f, y.y > 0.0f ? g.y : 0.0f, y.z > 0.0f ? g.z : 0.0f, y.w > 0.0f ? g.w : 0.0f);
-}
-
-// out = a + b (the U-Net's additive skip, adacofnet.py:128-146, kept apart from relu(conv) in the training forward)
-template <typename T>
-__global__ void add_kernel(const T *__restrict__ a, long long a_bs, const T *__restrict__ b, long long b_bs,
-                           T *__restrict__ out, long long o_bs, int N, long long count) {
-    GRID_STRIDE(i, (long long)N * count) {
-        const long long n = i / count, e = i - n * count;
-        out[n * o_bs + e] = vadd(a[n * a_bs + e], b[n * b_bs + e]);
+// Functors of map_kernel (vfi_grad_common.h).
+// a + b (the U-Net's additive skip, adacofnet.py:128-146, kept apart from relu(conv) in the training forward)
+struct Add {
+    __device__ __forceinline__ float operator()(float a, float b, float, bool) const { return a + b; }
+};
+// (g + add) * [y > 0] (y: the ReLU's output; y == 0 passes nothing, as torch's threshold backward)
+struct ReluMask {
+    __device__ __forceinline__ float operator()(float g, float y, float add, bool has_add) const {
+        const float v = has_add ? g + add : g;
+        return y > 0.0f ? v : 0.0f;
     }
-}
-
-// out = (g + add) * [y > 0]; out may be g itself (y: the ReLU's output; y == 0 passes nothing, as torch's threshold
-// backward)
-template <typename T>
-__global__ void relu_mask_kernel(const T *g, long long g_bs, const T *__restrict__ add, long long a_bs,
-                                 const T *__restrict__ y, long long y_bs, T *out, long long o_bs, int N, long long count) {
-    GRID_STRIDE(i, (long long)N * count) {
-        const long long n = i / count, e = i - n * count;
-        T v = g[n * g_bs + e];
-        if (add) v = vadd(v, add[n * a_bs + e]);
-        out[n * o_bs + e] = vmask(v, y[n * y_bs + e]);
-    }
-}
-
-// g_z = g s (1 - s): backward of s = sigmoid(z) (the occlusion head, adacofnet.py:98-99)
-__global__ void sigmoid_backward_kernel(const float *__restrict__ g, const float *__restrict__ s, float *__restrict__ gz,
-                                        long long count) {
-    GRID_STRIDE(i, count) {
-        const float v = s[i];
-        gz[i] = g[i] * v * (1.0f - v);
-    }
-}
+};
 
 // dst (N, C, H + 2p, W + 2p) = ReplicationPad2d(p) of src (N, C, H, W) (adacofnet.py:166,193-194)
 __global__ void replicate_pad_kernel(const float *__restrict__ src, long long s_bs, float *__restrict__ dst, int N, int C,
@@ -123,10 +72,11 @@ __global__ void pool2_avg_backward_kernel(const float *__restrict__ y, long long
     }
 }
 
-// Outputs of one axis of Upsample(x2, bilinear, align_corners=True) that read source j of n, with their weights.  Output o
-// sits at o (n-1)/(2n-1): the cell i0 and the fraction come from the integer quotient and remainder, so a weight carries
-// one rounding whatever n is (the forward kernel's float product o * scale is off by up to 2^-23 (n-1) instead; the two
-// agree to that).  At most 5 outputs have a non-zero weight (n = 1: both outputs, weight 1).
+// Tap rule of Upsample(x2, bilinear, align_corners=True) (adacofnet.py:30,42,54,68,76,88) for up2_backward_kernel: the
+// outputs of one axis that read source j of n, with their weights.  Output o sits at o (n-1)/(2n-1): the cell i0 and the
+// fraction come from the integer quotient and remainder, so a weight carries one rounding whatever n is (the forward
+// kernel's float product o * scale is off by up to 2^-23 (n-1) instead; the two agree to that).  At most 5 outputs have a
+// non-zero weight (n = 1: both outputs, weight 1).
 constexpr int kUpMax = 6;
 __device__ __forceinline__ int up2ac_sources(int j, int n, int *o, float *w) {
     const int no = 2 * n, den = no - 1;
@@ -146,32 +96,6 @@ __device__ __forceinline__ int up2ac_sources(int j, int n, int *o, float *w) {
         if (wt != 0.0f && k < kUpMax) { o[k] = q; w[k++] = wt; }
     }
     return k;
-}
-
-// Adjoint of Upsample(x2, bilinear, align_corners=True) (adacofnet.py:30,42,54,68,76,88) in gather form: one thread per
-// source element sums its weighted output gradients in a fixed order; `y` (optional) is the source itself when it is a
-// ReLU's output: the result is multiplied by [y > 0].
-__global__ void upsample2x_backward_kernel(const float *__restrict__ g, long long g_bs, const float *__restrict__ y,
-                                           long long y_bs, float *__restrict__ gx, long long gx_bs, int N, int C, int Hi,
-                                           int Wi) {
-    const int Ho = 2 * Hi, Wo = 2 * Wi;
-    GRID_STRIDE(i, (long long)N * C * Hi * Wi) {
-        const int xj = i % Wi, yj = (i / Wi) % Hi, c = (i / ((long long)Wi * Hi)) % C, n = i / ((long long)Wi * Hi * C);
-        const size_t src = ((size_t)c * Hi + yj) * Wi + xj;
-        float v = 0.0f;
-        if (!y || y[(size_t)n * y_bs + src] > 0.0f) {
-            int oy[kUpMax], ox[kUpMax];
-            float wy[kUpMax], wx[kUpMax];
-            const int ky = up2ac_sources(yj, Hi, oy, wy), kx = up2ac_sources(xj, Wi, ox, wx);
-            const float *gp = g + (size_t)n * g_bs + (size_t)c * Ho * Wo;
-            for (int a = 0; a < ky; ++a) {
-                float r = 0.0f;
-                for (int b = 0; b < kx; ++b) r += wx[b] * gp[(size_t)oy[a] * Wo + ox[b]];
-                v += wy[a] * r;
-            }
-        }
-        gx[(size_t)n * gx_bs + src] = v;
-    }
 }
 
 // ---- smoothness terms and heads -----------------------------------------------------------------------------------
@@ -207,22 +131,6 @@ __global__ void smooth_maps_kernel(const float *__restrict__ w1, const float *__
         m[((size_t)n * 4 + 2 * blockIdx.y) * HW + p] = sa * inv;
         m[((size_t)n * 4 + 2 * blockIdx.y + 1) * HW + p] = sb * inv;
     }
-}
-
-// sums v[0..NV) over the block in a fixed tree order; the result is valid in thread 0
-template <int NV> __device__ __forceinline__ void block_sum(float *v, float *lds) {
-#pragma unroll
-    for (int q = 0; q < NV; ++q) lds[q * kThreads + threadIdx.x] = v[q];
-    __syncthreads();
-    for (int s = kThreads / 2; s > 0; s >>= 1) {
-        if ((int)threadIdx.x < s) {
-#pragma unroll
-            for (int q = 0; q < NV; ++q) lds[q * kThreads + threadIdx.x] += lds[q * kThreads + threadIdx.x + s];
-        }
-        __syncthreads();
-    }
-#pragma unroll
-    for (int q = 0; q < NV; ++q) v[q] = lds[q * kThreads];
 }
 
 // stage 1: per block, the Charbonnier sums of the horizontal / vertical differences of the four m maps (v[0], v[1]) and
@@ -328,63 +236,13 @@ __global__ void head_backward_kernel(const float *__restrict__ gw, const float *
     }
 }
 
-// ---- Charbonnier loss (utility.py:67-77) --------------------------------------------------------------------------
-__global__ __launch_bounds__(kThreads) void charbonnier_partial_kernel(const float *__restrict__ a, const float *__restrict__ b,
-                                                                       long long count, float eps2, float *__restrict__ part) {
-    __shared__ float lds[kThreads];
-    float v[1] = {0.0f};
-    if (count % 4 == 0 && aligned16(a) && (!b || aligned16(b))) {
-        const float4 *a4 = reinterpret_cast<const float4 *>(a), *b4 = reinterpret_cast<const float4 *>(b);
-        GRID_STRIDE(i, count / 4) {
-            float4 d = a4[i];
-            if (b) { const float4 t = b4[i]; d.x -= t.x; d.y -= t.y; d.z -= t.z; d.w -= t.w; }
-            v[0] += (sqrtf(d.x * d.x + eps2) + sqrtf(d.y * d.y + eps2)) + (sqrtf(d.z * d.z + eps2) + sqrtf(d.w * d.w + eps2));
-        }
-    } else {
-        GRID_STRIDE(i, count) {
-            const float d = a[i] - (b ? b[i] : 0.0f);
-            v[0] += sqrtf(d * d + eps2);
-        }
-    }
-    block_sum<1>(v, lds);
-    if (threadIdx.x == 0) part[blockIdx.x] = v[0];
-}
-
-__global__ __launch_bounds__(kThreads) void charbonnier_final_kernel(const float *__restrict__ part, int blocks, float inv,
-                                                                     float *__restrict__ out) {
-    __shared__ float lds[kThreads];
-    float v[1] = {0.0f};
-    for (int b = threadIdx.x; b < blocks; b += kThreads) v[0] += part[b];
-    block_sum<1>(v, lds);
-    if (threadIdx.x == 0) out[0] = v[0] * inv;
-}
-
-// g_a = up * d / sqrt(d^2 + e^2) / count with d = a - b; g_b = -g_a
-__global__ void charbonnier_backward_kernel(const float *__restrict__ a, const float *__restrict__ b,
-                                            const float *__restrict__ up, float *__restrict__ ga, float *__restrict__ gb,
-                                            long long count, float eps2, float inv) {
-    const float s = up[0] * inv;
-    GRID_STRIDE(i, count) {
-        const float d = a[i] - (b ? b[i] : 0.0f);
-        const float v = s * d * rsqrtf(d * d + eps2);
-        if (ga) ga[i] = v;
-        if (gb) gb[i] = -v;
-    }
-}
-
 }  // namespace
 
 extern "C" int vfi_add(const float *a, long long a_bstride, const float *b, long long b_bstride, float *out,
                        long long out_bstride, int N, long long count, vfi_stream_t stream) {
     VFI_REQUIRE(a && b && out, VFI_ERR_INVALID_ARG, "vfi_add: null pointer");
     VFI_REQUIRE(N > 0 && count > 0, VFI_ERR_INVALID_ARG, "vfi_add: bad sizes");
-    if (count % 4 == 0 && a_bstride % 4 == 0 && b_bstride % 4 == 0 && out_bstride % 4 == 0 && aligned16(a) && aligned16(b) &&
-        aligned16(out))
-        LAUNCH_1D(add_kernel<float4>, (long long)N * count / 4, stream, reinterpret_cast<const float4 *>(a), a_bstride / 4,
-                  reinterpret_cast<const float4 *>(b), b_bstride / 4, reinterpret_cast<float4 *>(out), out_bstride / 4, N,
-                  count / 4);
-    else
-        LAUNCH_1D(add_kernel<float>, (long long)N * count, stream, a, a_bstride, b, b_bstride, out, out_bstride, N, count);
+    launch_map<Add>(a, a_bstride, b, b_bstride, nullptr, 0, out, out_bstride, N, count, stream);
     return vfi::check_launch("vfi_add");
 }
 
@@ -393,21 +251,15 @@ extern "C" int vfi_relu_mask(const float *grad, long long g_bstride, const float
                              vfi_stream_t stream) {
     VFI_REQUIRE(grad && y && out, VFI_ERR_INVALID_ARG, "vfi_relu_mask: null pointer");
     VFI_REQUIRE(N > 0 && count > 0, VFI_ERR_INVALID_ARG, "vfi_relu_mask: bad sizes");
-    if (count % 4 == 0 && g_bstride % 4 == 0 && a_bstride % 4 == 0 && y_bstride % 4 == 0 && out_bstride % 4 == 0 &&
-        aligned16(grad) && aligned16(addend) && aligned16(y) && aligned16(out))
-        LAUNCH_1D(relu_mask_kernel<float4>, (long long)N * count / 4, stream, reinterpret_cast<const float4 *>(grad),
-                  g_bstride / 4, reinterpret_cast<const float4 *>(addend), a_bstride / 4, reinterpret_cast<const float4 *>(y),
-                  y_bstride / 4, reinterpret_cast<float4 *>(out), out_bstride / 4, N, count / 4);
-    else
-        LAUNCH_1D(relu_mask_kernel<float>, (long long)N * count, stream, grad, g_bstride, addend, a_bstride, y, y_bstride, out,
-                  out_bstride, N, count);
+    launch_map<ReluMask>(grad, g_bstride, y, y_bstride, addend, a_bstride, out, out_bstride, N, count, stream);
     return vfi::check_launch("vfi_relu_mask");
 }
 
 extern "C" int vfi_sigmoid_backward(const float *grad, const float *s, float *grad_z, long long count, vfi_stream_t stream) {
     VFI_REQUIRE(grad && s && grad_z, VFI_ERR_INVALID_ARG, "vfi_sigmoid_backward: null pointer");
     VFI_REQUIRE(count > 0, VFI_ERR_INVALID_ARG, "vfi_sigmoid_backward: bad size");
-    LAUNCH_1D(sigmoid_backward_kernel, count, stream, grad, s, grad_z, count);
+    // the occlusion head (adacofnet.py:98-99), dense
+    launch_map<ActGrad<VFI_ACT_SIGMOID>>(grad, count, s, count, nullptr, 0, grad_z, count, 1, count, stream);
     return vfi::check_launch("vfi_sigmoid_backward");
 }
 
@@ -446,7 +298,7 @@ extern "C" int vfi_upsample2x_backward(const float *grad_y, long long gy_bstride
     VFI_REQUIRE(grad_y && grad_x, VFI_ERR_INVALID_ARG, "vfi_upsample2x_backward: null pointer");
     VFI_REQUIRE(N > 0 && C > 0 && Hin > 0 && Win > 0 && Hin < (1 << 20) && Win < (1 << 20), VFI_ERR_INVALID_ARG,
                 "vfi_upsample2x_backward: bad sizes");
-    LAUNCH_1D(upsample2x_backward_kernel, (long long)N * C * Hin * Win, stream, grad_y, gy_bstride, mask_src, ms_bstride,
+    LAUNCH_1D((up2_backward_kernel<kUpMax, up2ac_sources>), (long long)N * C * Hin * Win, stream, grad_y, gy_bstride, mask_src, ms_bstride,
               grad_x, gx_bstride, N, C, Hin, Win);
     return vfi::check_launch("vfi_upsample2x_backward");
 }
@@ -466,7 +318,7 @@ extern "C" int vfi_adacof_smooth_forward(const float *w1, const float *a1, const
                 "vfi_adacof_smooth_forward: null pointer");
     VFI_REQUIRE(N > 0 && F > 0 && H > 1 && W > 1, VFI_ERR_INVALID_ARG, "vfi_adacof_smooth_forward: bad sizes");
     const long long HW = (long long)H * W;
-    hipLaunchKernelGGL(smooth_maps_kernel, dim3(blocks_for((long long)N * HW), 2), dim3(kThreads), 0, vfi::as_stream(stream),
+    hipLaunchKernelGGL(smooth_maps_kernel, dim3(vfi::blocks_1d((long long)N * HW), 2), dim3(kThreads), 0, vfi::as_stream(stream),
                        w1, a1, b1, w2, a2, b2, m, N, F * F, HW);
     int rc = vfi::check_launch("vfi_adacof_smooth_forward (maps)");
     if (rc != VFI_OK) return rc;
@@ -513,20 +365,16 @@ extern "C" int vfi_charbonnier_forward(const float *a, const float *b, long long
                                        float *out, vfi_stream_t stream) {
     VFI_REQUIRE(a && workspace && out, VFI_ERR_INVALID_ARG, "vfi_charbonnier_forward: null pointer");
     VFI_REQUIRE(count > 0, VFI_ERR_INVALID_ARG, "vfi_charbonnier_forward: bad size");
-    const bool vec = count % 4 == 0 && aligned16(a) && (!b || aligned16(b));
-    const int blocks = reduce_blocks(vec ? count / 4 : count);
-    hipLaunchKernelGGL(charbonnier_partial_kernel, dim3(blocks), dim3(kThreads), 0, vfi::as_stream(stream), a, b, count,
-                       epsilon * epsilon, workspace);
-    hipLaunchKernelGGL(charbonnier_final_kernel, dim3(1), dim3(kThreads), 0, vfi::as_stream(stream), workspace, blocks,
-                       (float)(1.0 / (double)count), out);
-    return vfi::check_launch("vfi_charbonnier_forward");
+    // utility.py:67-77
+    return launch_sum_forward(CharbonnierTerm{epsilon * epsilon}, a, b, count, (float)(1.0 / (double)count), workspace, out, stream,
+                              "vfi_charbonnier_forward");
 }
 
 extern "C" int vfi_charbonnier_backward(const float *a, const float *b, const float *upstream, float *grad_a, float *grad_b,
                                         long long count, float epsilon, vfi_stream_t stream) {
     VFI_REQUIRE(a && upstream && (grad_a || grad_b), VFI_ERR_INVALID_ARG, "vfi_charbonnier_backward: null pointer");
     VFI_REQUIRE(count > 0, VFI_ERR_INVALID_ARG, "vfi_charbonnier_backward: bad size");
-    LAUNCH_1D(charbonnier_backward_kernel, count, stream, a, b, upstream, grad_a, grad_b, count, epsilon * epsilon,
-              (float)(1.0 / (double)count));
+    LAUNCH_1D(sum_backward_kernel<CharbonnierTerm>, count, stream, CharbonnierTerm{epsilon * epsilon}, a, b, upstream, grad_a,
+              grad_b, count, (float)(1.0 / (double)count));
     return vfi::check_launch("vfi_charbonnier_backward");
 }

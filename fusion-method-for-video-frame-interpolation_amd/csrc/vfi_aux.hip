@@ -2,17 +2,11 @@
 // Each one replaces a torch op of the reference's forward passes; all take explicit batch strides
 // so they can read / write channel slices of wider NCHW tensors (no concat / split copies).
 // One thread per output element, lanes along x (coalesced 256 B per wave-instruction).
-#include "vfi_common.h"
+#include "vfi_grad_common.h"
 
 namespace {
 
 using vfi::ceil_div;
-
-constexpr int kThreads = 256;
-inline int blocks_for(long long n) {
-    long long b = (n + kThreads - 1) / kThreads;
-    return (int)(b < 1 ? 1 : (b > 8 * 2048 ? 8 * 2048 : b));  // grid-stride beyond 16k blocks
-}
 
 // ---- AdaCoFNet.forward prologue ---------------------------------------------------------------
 // reflect-pad bottom/right to (Hp, Wp) (fusion_adacofnet.py:182-192), keep the raw padded frames for
@@ -349,9 +343,6 @@ __global__ void tanh_residual_clamp_kernel(const float *__restrict__ x, const fl
 }
 
 }  // namespace
-
-#define LAUNCH_1D(kernel, total, stream, ...) \
-    hipLaunchKernelGGL(kernel, dim3(blocks_for(total)), dim3(kThreads), 0, vfi::as_stream(stream), __VA_ARGS__)
 
 extern "C" int vfi_adacof_prepare(const float *frame0, const float *frame2, float *pad0, float *pad2, float *x6,
                                   int N, int H, int W, int Hp, int Wp, int rgbx, vfi_stream_t stream) {

@@ -2,20 +2,14 @@
 // fixed-order slab reduction: no float atomics, bit-reproducible), its input gradient (the forward convolution machinery on
 // the transposed, flipped weights plus a padding fold) and the three HBM-bound glue adjoints (tanh + residual + clamp head,
 // ReLU + max-pool encoder block, ReLU + bilinear x2 decoder resize).  Differentiates reference src/fusion_net/fusion_net.py
-// :24-41 (layers) and :46-77 (forward).
-#include "vfi_common.h"
+// :24-41 (layers) and :46-77 (forward).  The rules: vfi_grad_common.h.
+#include "vfi_grad_common.h"
 
 namespace {
 
 using vfi::ceil_div;
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-constexpr int kThreads = 256;
-inline int blocks_for(long long n) {
-    long long b = (n + kThreads - 1) / kThreads;
-    return (int)(b < 1 ? 1 : (b > 8 * 2048 ? 8 * 2048 : b));  // grid-stride beyond 16k blocks
-}
 
 // ---- weight gradient --------------------------------------------------------------------------------------------
 // GEMM dW[co][c] = sum_p dY[co][p] * B[p][c] with c = ci*KS*KS + ky*KS + kx (plain OIHW) and p = (n, y, x):
@@ -283,9 +277,13 @@ __global__ void pool2_max_backward_kernel(const float *__restrict__ s, long long
     }
 }
 
-// Output positions of one axis of a x2, align_corners=False resize (source coordinate max(o/2 - 1/4, 0)) that read
-// source index j of n, with their weights: o = 2j-1 (1/4), 2j (3/4; 1 at j = 0), 2j+1 (3/4; 1 at j = n-1, where both
-// taps clamp onto j), 2j+2 (1/4).
+// Tap rule of vfi_resize_bilinear(x2, align_corners=0) for up2_backward_kernel: the output positions of one axis (source
+// coordinate max(o/2 - 1/4, 0)) that read source index j of n, with their weights: o = 2j-1 (1/4), 2j (3/4; 1 at j = 0),
+// 2j+1 (3/4; 1 at j = n-1, where both taps clamp onto j), 2j+2 (1/4).
+// The any-size adjoint (resize_adjoint_kernel, vfi_phasenet_grad.hip) gives the same bits for an exact x2 (tested), but it
+// re-derives candidates and weights per output: vfi_resize_bilinear_backward routed through it took 1.81 - 1.93 x as long
+// per call at FusionNet's decoder shapes (batch 16: 128 x 32^2, 64 x 64^2, 32 x 128^2) and the glue row of
+// tools/fusionnet_train_rate.py 1.36 x (0.507 against 0.374 ms, MI355X).  So the fixed taps stay for x2.
 __device__ __forceinline__ int up2_sources(int j, int n, int *o, float *w) {
     int k = 0;
     if (j >= 1) { o[k] = 2 * j - 1; w[k++] = 0.25f; }
@@ -294,35 +292,6 @@ __device__ __forceinline__ int up2_sources(int j, int n, int *o, float *w) {
     if (j + 1 <= n - 1) { o[k] = 2 * j + 2; w[k++] = 0.25f; }
     return k;
 }
-
-// Adjoint of vfi_resize_bilinear(x2, align_corners=0) in gather form: one thread per source element sums its (up to
-// 4 x 4) weighted output gradients in a fixed order; relu_input multiplies by [x > 0].
-__global__ void resize_up2_backward_kernel(const float *__restrict__ x, long long x_bs, const float *__restrict__ g,
-                                           long long g_bs, float *__restrict__ gx, long long gx_bs, int N, int C, int Hi,
-                                           int Wi, int relu_in) {
-    const int Ho = 2 * Hi, Wo = 2 * Wi;
-    const long long total = (long long)N * C * Hi * Wi;
-    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
-        const int xj = i % Wi, yj = (i / Wi) % Hi, c = (i / ((long long)Wi * Hi)) % C, n = i / ((long long)Wi * Hi * C);
-        const size_t src = ((size_t)c * Hi + yj) * Wi + xj;
-        float v = 0.0f;
-        if (!relu_in || x[(size_t)n * x_bs + src] > 0.0f) {
-            int oy[4], ox[4];
-            float wy[4], wx[4];
-            const int ky = up2_sources(yj, Hi, oy, wy), kx = up2_sources(xj, Wi, ox, wx);
-            const float *gp = g + (size_t)n * g_bs + (size_t)c * Ho * Wo;
-            for (int a = 0; a < ky; ++a) {
-                float r = 0.0f;
-                for (int b = 0; b < kx; ++b) r += wx[b] * gp[(size_t)oy[a] * Wo + ox[b]];
-                v += wy[a] * r;
-            }
-        }
-        gx[(size_t)n * gx_bs + src] = v;
-    }
-}
-
-#define LAUNCH_1D(kernel, total, stream, ...) \
-    hipLaunchKernelGGL(kernel, dim3(blocks_for(total)), dim3(kThreads), 0, vfi::as_stream(stream), __VA_ARGS__)
 
 }  // namespace
 
@@ -444,7 +413,7 @@ extern "C" int vfi_resize_bilinear_backward(const float *x, long long x_bstride,
     VFI_REQUIRE(N > 0 && C > 0 && Hin > 0 && Win > 0, VFI_ERR_INVALID_ARG, "vfi_resize_bilinear_backward: bad sizes");
     VFI_REQUIRE(Hout == 2 * Hin && Wout == 2 * Win, VFI_ERR_UNSUPPORTED,
                 "vfi_resize_bilinear_backward: only x2 (got %dx%d -> %dx%d)", Hin, Win, Hout, Wout);
-    LAUNCH_1D(resize_up2_backward_kernel, (long long)N * C * Hin * Win, stream, x, x_bstride, grad_y, gy_bstride, grad_x,
-              gx_bstride, N, C, Hin, Win, relu_input ? 1 : 0);
+    LAUNCH_1D((up2_backward_kernel<4, up2_sources>), (long long)N * C * Hin * Win, stream, grad_y, gy_bstride, relu_input ? x : nullptr,
+              x_bstride, grad_x, gx_bstride, N, C, Hin, Win);
     return vfi::check_launch("vfi_resize_bilinear_backward");
 }

@@ -2,33 +2,11 @@
 // (vfi_conv_grad.hip).  Differentiates reference src/phase_net/phase_net.py:138-139 (bilinear resize to an arbitrary size),
 // :190-200 (ELU, tanh), :113-116 and :155-168 with reverse_normalize :80-98 (the per-level blends; a band level's whole
 // head in one pass), and
-// src/train/loss.py:10-20 (phase loss, L1).  Rules of sections 12 and 13: no float atomics, one writer per element,
-// reductions in an order fixed by the shape, fp32 throughout.
-#include "vfi_common.h"
-
-#include <cstdint>
+// src/train/loss.py:10-20 (phase loss, L1: AbsTerm over the shared two-stage reduction).  The rules: vfi_grad_common.h;
+// fp32 throughout.
+#include "vfi_grad_common.h"
 
 namespace {
-
-constexpr int kThreads = 256;
-constexpr int kMaxPartials = 1024;      // blocks of a two-stage reduction (VFI_REDUCE_WORKSPACE_FLOATS >= this)
-
-inline int blocks_for(long long n) {
-    long long b = (n + kThreads - 1) / kThreads;
-    return (int)(b < 1 ? 1 : (b > 8 * 2048 ? 8 * 2048 : b));  // grid-stride beyond 16k blocks
-}
-// reduction grids depend on the element count alone, so the summation order -- and the bits -- repeat
-inline int reduce_blocks(long long n) {
-    long long b = (n + kThreads - 1) / kThreads;
-    return (int)(b < 1 ? 1 : (b > kMaxPartials ? kMaxPartials : b));
-}
-__host__ __device__ inline bool aligned16(const void *p) { return ((uintptr_t)p & 15) == 0; }
-
-#define LAUNCH_1D(kernel, total, stream, ...) \
-    hipLaunchKernelGGL(kernel, dim3(blocks_for(total)), dim3(kThreads), 0, vfi::as_stream(stream), __VA_ARGS__)
-
-#define GRID_STRIDE(i, total) \
-    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < (total); i += (long long)gridDim.x * blockDim.x)
 
 // ---- adjoint of the arbitrary-size bilinear resize (align_corners = 0) ---------------------------------------------
 // Weight with which output o of an axis resized n_in -> n_out reads source s: the forward's own fp32 arithmetic
@@ -83,33 +61,6 @@ __global__ void resize_adjoint_kernel(const float *__restrict__ g, long long g_b
     }
 }
 
-// ---- activation backward from the activation's output --------------------------------------------------------------
-// ELU (alpha = 1): y > 0 ? 1 : y + 1 (for y <= 0, y = e^z - 1 and dy/dz = e^z);  tanh: 1 - y^2
-template <int ACT> __device__ __forceinline__ float act_grad(float g, float y) {
-    return ACT == VFI_ACT_ELU ? (y > 0.0f ? g : g * (y + 1.0f)) : g * (1.0f - y * y);
-}
-template <int ACT, typename T> __device__ __forceinline__ T act_grad_v(T g, T y);
-template <> __device__ __forceinline__ float act_grad_v<VFI_ACT_ELU, float>(float g, float y) { return act_grad<VFI_ACT_ELU>(g, y); }
-template <> __device__ __forceinline__ float act_grad_v<VFI_ACT_TANH, float>(float g, float y) { return act_grad<VFI_ACT_TANH>(g, y); }
-template <> __device__ __forceinline__ float4 act_grad_v<VFI_ACT_ELU, float4>(float4 g, float4 y) {
-    return make_float4(act_grad<VFI_ACT_ELU>(g.x, y.x), act_grad<VFI_ACT_ELU>(g.y, y.y), act_grad<VFI_ACT_ELU>(g.z, y.z),
-                       act_grad<VFI_ACT_ELU>(g.w, y.w));
-}
-template <> __device__ __forceinline__ float4 act_grad_v<VFI_ACT_TANH, float4>(float4 g, float4 y) {
-    return make_float4(act_grad<VFI_ACT_TANH>(g.x, y.x), act_grad<VFI_ACT_TANH>(g.y, y.y), act_grad<VFI_ACT_TANH>(g.z, y.z),
-                       act_grad<VFI_ACT_TANH>(g.w, y.w));
-}
-
-// out = g * f'(y); out may be g itself.  T = float, or float4 (count and strides in units of T)
-template <int ACT, typename T>
-__global__ void act_backward_kernel(const T *g, long long g_bs, const T *__restrict__ y, long long y_bs, T *out,
-                                    long long o_bs, int N, long long count) {
-    GRID_STRIDE(i, (long long)N * count) {
-        const long long n = i / count, e = i - n * count;
-        out[n * o_bs + e] = act_grad_v<ACT, T>(g[n * g_bs + e], y[n * y_bs + e]);
-    }
-}
-
 // ---- adjoints of the per-level blends (vfi_phasenet_emit, vfi_phasenet_emit_low) -----------------------------------
 // phase = pi pred[:, 0:4];  amp = (b amp_in[:, 4:8] + (1 - b) amp_in[:, 0:4]) max[n], b = (pred[:, 4:8] + 1) / 2:
 // g_pred[:, 0:4] = pi g_phase,  g_pred[:, 4:8] = g_amp max[n] (amp_in[:, 4:8] - amp_in[:, 0:4]) / 2.  A NULL gradient is zero.
@@ -135,61 +86,6 @@ __global__ void emit_low_backward_kernel(const float *__restrict__ g_low, const 
     }
 }
 
-// ---- phase loss and L1 (loss.py:10-20) -----------------------------------------------------------------------------
-// sums v over the block in a fixed tree order; the result is valid in thread 0
-__device__ __forceinline__ float block_sum(float v, float *lds) {
-    lds[threadIdx.x] = v;
-    __syncthreads();
-    for (int s = kThreads / 2; s > 0; s >>= 1) {
-        if ((int)threadIdx.x < s) lds[threadIdx.x] += lds[threadIdx.x + s];
-        __syncthreads();
-    }
-    return lds[0];
-}
-// wrap(d) = atan2(sin d, cos d): d brought to (-pi, pi] (loss.py:15)
-template <bool WRAP> __device__ __forceinline__ float wrapped(float d) { return WRAP ? atan2f(sinf(d), cosf(d)) : d; }
-
-// stage 1: per block, sum |wrap(a - b)|; 16-byte loads when the count and both bases allow
-template <bool WRAP>
-__global__ __launch_bounds__(kThreads) void l1_partial_kernel(const float *__restrict__ a, const float *__restrict__ b,
-                                                              long long count, int vec, float *__restrict__ part) {
-    __shared__ float lds[kThreads];
-    float v = 0.0f;
-    if (vec) {
-        const float4 *a4 = reinterpret_cast<const float4 *>(a), *b4 = reinterpret_cast<const float4 *>(b);
-        GRID_STRIDE(i, count / 4) {
-            const float4 p = a4[i], q = b4[i];
-            v += (fabsf(wrapped<WRAP>(p.x - q.x)) + fabsf(wrapped<WRAP>(p.y - q.y))) +
-                 (fabsf(wrapped<WRAP>(p.z - q.z)) + fabsf(wrapped<WRAP>(p.w - q.w)));
-        }
-    } else {
-        GRID_STRIDE(i, count) v += fabsf(wrapped<WRAP>(a[i] - b[i]));
-    }
-    v = block_sum(v, lds);
-    if (threadIdx.x == 0) part[blockIdx.x] = v;
-}
-// stage 2 (one block): out[0] = factor * sum of the partials
-__global__ __launch_bounds__(kThreads) void l1_final_kernel(const float *__restrict__ part, int blocks, float factor,
-                                                            float *__restrict__ out) {
-    __shared__ float lds[kThreads];
-    float v = 0.0f;
-    for (int b = threadIdx.x; b < blocks; b += kThreads) v += part[b];
-    v = block_sum(v, lds);
-    if (threadIdx.x == 0) out[0] = v * factor;
-}
-// g_a = sign(wrap(a - b)) * upstream * factor, g_b = -g_a
-template <bool WRAP>
-__global__ void l1_backward_kernel(const float *__restrict__ a, const float *__restrict__ b, const float *__restrict__ up,
-                                   float *__restrict__ ga, float *__restrict__ gb, long long count, float factor) {
-    const float s = up[0] * factor;
-    GRID_STRIDE(i, count) {
-        const float d = wrapped<WRAP>(a[i] - b[i]);
-        const float v = d > 0.0f ? s : (d < 0.0f ? -s : 0.0f);
-        if (ga) ga[i] = v;
-        if (gb) gb[i] = -v;
-    }
-}
-
 // ---- adjoint of a band level's head in one pass (vfi_phasenet_predict: 1x1 64 -> 8, tanh, emit) ---------------------
 // Per pixel gz = (emit adjoint + grad_pred_in) (1 - pred^2); grad_f[k] = sum_j W[j][k] gz[j];  grad_W[j][k] = sum gz[j] f[k],
 // grad_b[j] = sum gz[j].  A block of 256 threads walks tiles of kHeadTile pixels of one sample:
@@ -209,12 +105,6 @@ static_assert(kMaxPartials * kHeadOut <= VFI_PHASENET_HEAD_WORKSPACE_FLOATS, "he
 template <int VEC> struct HeadVec;
 template <> struct HeadVec<1> { typedef float type; };
 template <> struct HeadVec<4> { typedef float4 type; };
-__device__ __forceinline__ float hv_get(float v, int) { return v; }
-__device__ __forceinline__ float hv_get(const float4 &v, int i) { return i == 0 ? v.x : (i == 1 ? v.y : (i == 2 ? v.z : v.w)); }
-__device__ __forceinline__ void hv_set(float &v, int, float x) { v = x; }
-__device__ __forceinline__ void hv_set(float4 &v, int i, float x) {
-    if (i == 0) v.x = x; else if (i == 1) v.y = x; else if (i == 2) v.z = x; else v.w = x;
-}
 
 struct HeadArgs {
     const float *f, *pred, *amp, *maxv, *w, *g_phase, *g_amp, *g_pred;
@@ -251,10 +141,10 @@ __global__ __launch_bounds__(kThreads) void head_backward_kernel(HeadArgs a) {
                     if (a.g_phase) {
                         const vec gp = *reinterpret_cast<const vec *>(a.g_phase + ((size_t)n * 4 + j) * HW + q);
 #pragma unroll
-                        for (int v = 0; v < VEC; ++v) hv_set(g, v, hv_get(gp, v) * 3.14159265358979323846f);
+                        for (int v = 0; v < VEC; ++v) lane_set(g, v, lane_get(gp, v) * 3.14159265358979323846f);
                     } else {
 #pragma unroll
-                        for (int v = 0; v < VEC; ++v) hv_set(g, v, 0.0f);
+                        for (int v = 0; v < VEC; ++v) lane_set(g, v, 0.0f);
                     }
                 } else {
                     if (a.g_amp) {
@@ -264,22 +154,22 @@ __global__ __launch_bounds__(kThreads) void head_backward_kernel(HeadArgs a) {
                         const vec a0 = *reinterpret_cast<const vec *>(am + (size_t)(j - 4) * HW);
                         const float mx = a.maxv[n];
 #pragma unroll
-                        for (int v = 0; v < VEC; ++v) hv_set(g, v, hv_get(ga, v) * mx * (hv_get(a1, v) - hv_get(a0, v)) * 0.5f);
+                        for (int v = 0; v < VEC; ++v) lane_set(g, v, lane_get(ga, v) * mx * (lane_get(a1, v) - lane_get(a0, v)) * 0.5f);
                     } else {
 #pragma unroll
-                        for (int v = 0; v < VEC; ++v) hv_set(g, v, 0.0f);
+                        for (int v = 0; v < VEC; ++v) lane_set(g, v, 0.0f);
                     }
                 }
                 if (a.g_pred) {
                     const vec gi = *reinterpret_cast<const vec *>(a.g_pred + (size_t)n * a.gp_bs + (size_t)j * HW + q);
 #pragma unroll
-                    for (int v = 0; v < VEC; ++v) hv_set(g, v, hv_get(g, v) + hv_get(gi, v));
+                    for (int v = 0; v < VEC; ++v) lane_set(g, v, lane_get(g, v) + lane_get(gi, v));
                 }
 #pragma unroll
-                for (int v = 0; v < VEC; ++v) hv_set(gz, v, hv_get(g, v) * (1.0f - hv_get(y, v) * hv_get(y, v)));
+                for (int v = 0; v < VEC; ++v) lane_set(gz, v, lane_get(g, v) * (1.0f - lane_get(y, v) * lane_get(y, v)));
             } else {
 #pragma unroll
-                for (int v = 0; v < VEC; ++v) hv_set(gz, v, 0.0f);
+                for (int v = 0; v < VEC; ++v) lane_set(gz, v, 0.0f);
             }
             *reinterpret_cast<vec *>(s_gz + j * kHeadTile + pg * VEC) = gz;
         }
@@ -297,7 +187,7 @@ __global__ __launch_bounds__(kThreads) void head_backward_kernel(HeadArgs a) {
                 if (WGRAD) {
                     vec fv;
 #pragma unroll
-                    for (int v = 0; v < VEC; ++v) hv_set(fv, v, 0.0f);
+                    for (int v = 0; v < VEC; ++v) lane_set(fv, v, 0.0f);
                     if (valid) fv = *reinterpret_cast<const vec *>(a.f + (size_t)n * a.f_bs + (size_t)k * HW + q);
                     *reinterpret_cast<vec *>(s_f + k * kHeadRow + pg * VEC) = fv;
                 }
@@ -306,15 +196,15 @@ __global__ __launch_bounds__(kThreads) void head_backward_kernel(HeadArgs a) {
                     vec r;
 #pragma unroll
                     for (int v = 0; v < VEC; ++v) {
-                        float s = w0.x * hv_get(gz[0], v);
-                        s = fmaf(w0.y, hv_get(gz[1], v), s);
-                        s = fmaf(w0.z, hv_get(gz[2], v), s);
-                        s = fmaf(w0.w, hv_get(gz[3], v), s);
-                        s = fmaf(w1.x, hv_get(gz[4], v), s);
-                        s = fmaf(w1.y, hv_get(gz[5], v), s);
-                        s = fmaf(w1.z, hv_get(gz[6], v), s);
-                        s = fmaf(w1.w, hv_get(gz[7], v), s);
-                        hv_set(r, v, s);
+                        float s = w0.x * lane_get(gz[0], v);
+                        s = fmaf(w0.y, lane_get(gz[1], v), s);
+                        s = fmaf(w0.z, lane_get(gz[2], v), s);
+                        s = fmaf(w0.w, lane_get(gz[3], v), s);
+                        s = fmaf(w1.x, lane_get(gz[4], v), s);
+                        s = fmaf(w1.y, lane_get(gz[5], v), s);
+                        s = fmaf(w1.z, lane_get(gz[6], v), s);
+                        s = fmaf(w1.w, lane_get(gz[7], v), s);
+                        lane_set(r, v, s);
                     }
                     *reinterpret_cast<vec *>(a.g_f + (size_t)n * a.gf_bs + (size_t)k * HW + q) = r;
                 }
@@ -356,18 +246,6 @@ __global__ __launch_bounds__(kThreads) void head_reduce_kernel(const float *__re
     }
 }
 
-template <int ACT>
-void launch_act_backward(bool v4, const float *g, long long g_bs, const float *y, long long y_bs, float *out, long long o_bs,
-                         int N, long long count, vfi_stream_t stream) {
-    const auto k4 = act_backward_kernel<ACT, float4>;
-    const auto k1 = act_backward_kernel<ACT, float>;
-    if (v4)
-        LAUNCH_1D(k4, (long long)N * count / 4, stream, reinterpret_cast<const float4 *>(g), g_bs / 4,
-                  reinterpret_cast<const float4 *>(y), y_bs / 4, reinterpret_cast<float4 *>(out), o_bs / 4, N, count / 4);
-    else
-        LAUNCH_1D(k1, (long long)N * count, stream, g, g_bs, y, y_bs, out, o_bs, N, count);
-}
-
 }  // namespace
 
 extern "C" int vfi_resize_bilinear_adjoint(const float *grad_y, long long gy_bstride, float *grad_x, long long gx_bstride,
@@ -387,10 +265,8 @@ extern "C" int vfi_act_backward(const float *grad, long long g_bstride, const fl
     VFI_REQUIRE(grad && y && out, VFI_ERR_INVALID_ARG, "vfi_act_backward: null pointer");
     VFI_REQUIRE(N > 0 && count > 0, VFI_ERR_INVALID_ARG, "vfi_act_backward: bad sizes");
     VFI_REQUIRE(act == VFI_ACT_ELU || act == VFI_ACT_TANH, VFI_ERR_UNSUPPORTED, "vfi_act_backward: act %d (ELU and tanh only)", act);
-    const bool v4 = count % 4 == 0 && g_bstride % 4 == 0 && y_bstride % 4 == 0 && out_bstride % 4 == 0 && aligned16(grad) &&
-                    aligned16(y) && aligned16(out);
-    if (act == VFI_ACT_ELU) launch_act_backward<VFI_ACT_ELU>(v4, grad, g_bstride, y, y_bstride, out, out_bstride, N, count, stream);
-    else launch_act_backward<VFI_ACT_TANH>(v4, grad, g_bstride, y, y_bstride, out, out_bstride, N, count, stream);
+    if (act == VFI_ACT_ELU) launch_map<ActGrad<VFI_ACT_ELU>>(grad, g_bstride, y, y_bstride, nullptr, 0, out, out_bstride, N, count, stream);
+    else launch_map<ActGrad<VFI_ACT_TANH>>(grad, g_bstride, y, y_bstride, nullptr, 0, out, out_bstride, N, count, stream);
     return vfi::check_launch("vfi_act_backward");
 }
 
@@ -454,14 +330,9 @@ extern "C" int vfi_l1_forward(const float *a, const float *b, long long count, i
                               float *out, vfi_stream_t stream) {
     VFI_REQUIRE(a && b && workspace && out, VFI_ERR_INVALID_ARG, "vfi_l1_forward: null pointer");
     VFI_REQUIRE(count > 0, VFI_ERR_INVALID_ARG, "vfi_l1_forward: bad size");
-    const int vec = count % 4 == 0 && aligned16(a) && aligned16(b);
-    const int blocks = reduce_blocks(vec ? count / 4 : count);
-    hipStream_t s = vfi::as_stream(stream);
-    if (wrap) hipLaunchKernelGGL(l1_partial_kernel<true>, dim3(blocks), dim3(kThreads), 0, s, a, b, count, vec, workspace);
-    else hipLaunchKernelGGL(l1_partial_kernel<false>, dim3(blocks), dim3(kThreads), 0, s, a, b, count, vec, workspace);
-    hipLaunchKernelGGL(l1_final_kernel, dim3(1), dim3(kThreads), 0, s, workspace, blocks, (float)((double)scale / (double)count),
-                       out);
-    return vfi::check_launch("vfi_l1_forward");
+    const float factor = (float)((double)scale / (double)count);
+    if (wrap) return launch_sum_forward(AbsTerm<true>{}, a, b, count, factor, workspace, out, stream, "vfi_l1_forward");
+    return launch_sum_forward(AbsTerm<false>{}, a, b, count, factor, workspace, out, stream, "vfi_l1_forward");
 }
 
 extern "C" int vfi_l1_backward(const float *a, const float *b, const float *upstream, float *grad_a, float *grad_b,
@@ -469,7 +340,7 @@ extern "C" int vfi_l1_backward(const float *a, const float *b, const float *upst
     VFI_REQUIRE(a && b && upstream && (grad_a || grad_b), VFI_ERR_INVALID_ARG, "vfi_l1_backward: null pointer");
     VFI_REQUIRE(count > 0, VFI_ERR_INVALID_ARG, "vfi_l1_backward: bad size");
     const float factor = (float)((double)scale / (double)count);
-    if (wrap) LAUNCH_1D(l1_backward_kernel<true>, count, stream, a, b, upstream, grad_a, grad_b, count, factor);
-    else LAUNCH_1D(l1_backward_kernel<false>, count, stream, a, b, upstream, grad_a, grad_b, count, factor);
+    if (wrap) LAUNCH_1D(sum_backward_kernel<AbsTerm<true>>, count, stream, AbsTerm<true>{}, a, b, upstream, grad_a, grad_b, count, factor);
+    else LAUNCH_1D(sum_backward_kernel<AbsTerm<false>>, count, stream, AbsTerm<false>{}, a, b, upstream, grad_a, grad_b, count, factor);
     return vfi::check_launch("vfi_l1_backward");
 }

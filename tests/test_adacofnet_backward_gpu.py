@@ -275,6 +275,14 @@ def test_pool2_avg_backward_and_relu_mask_on_channel_slices(h, w, device):
     out = ops.relu_mask_(gkb.to(device)[:, 1:6], big.to(device)[:, 2:7], out=torch.empty((2, 5, h, w), device=device))
     assert torch.equal(out.cpu(), gk * (y > 0))
     assert torch.equal(ops.add(big.to(device)[:, 2:7], gkb.to(device)[:, 1:6]).cpu(), y + gk)
+    # the 4-byte path (bases 4 bytes off 16-byte alignment) and the 16-byte path (dense copies) give the same bits
+    def off(t):
+        v = torch.empty(t.numel() + 1, device=device)[1:].view(t.shape)
+        assert v.data_ptr() % 16 != 0
+        return v.copy_(t)
+    a, b, c = gkb.to(device)[:, 1:6].contiguous(), big.to(device)[:, 2:7].contiguous(), got.contiguous()
+    assert a[0].numel() % 4 == 0 and torch.equal(ops.add(off(a), off(b)), ops.add(a, b))
+    assert torch.equal(ops.relu_mask_(off(a), off(b), addend=off(c)), ops.relu_mask_(a.clone(), b, addend=c))
 
 
 @pytest.mark.parametrize("n,f,h,w,h0,w0", [(2, 3, 6, 7, 6, 7), (1, 5, 32, 32, 20, 27), (2, 5, 33, 65, 33, 65)])

@@ -321,6 +321,9 @@ def test_resize_bilinear_backward(h, w, device):
     (F.interpolate(xd, scale_factor=2, mode="bilinear", align_corners=False) * gy.double()).sum().backward()
     got = ops.resize_bilinear_backward(x.to(device), gy.to(device), relu_input=False)
     assert torch.allclose(got.cpu().double(), xd.grad, rtol=1e-6, atol=1e-6)
+    # an exact x2 has coordinates and weights exact in fp32 (0, 1/4, 3/4, 1) and both adjoints add in ascending order:
+    # the any-size adjoint gives the same bits
+    assert torch.equal(got, ops.resize_bilinear_adjoint(gy.to(device), (h, w)))
 
 
 # ---- a short training run, mirroring the reference's loop (Adam 1e-4, L1) ------------------------------------------

@@ -31,6 +31,13 @@ def _rel(a, b):
     return float((a - b).norm() / b.norm().clamp_min(1e-300))
 
 
+def _misaligned(t):
+    """t's values, dense, at a base 4 bytes off 16-byte alignment: the elementwise pass then takes its 4-byte path."""
+    v = torch.empty(t.numel() + 1, device=t.device)[1:].view(t.shape)
+    assert v.data_ptr() % 16 != 0
+    return v.copy_(t)
+
+
 # ---- resize adjoint --------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("src,dst", RESIZE_SIZES)
 def test_resize_adjoint(src, dst, device):
@@ -82,6 +89,9 @@ def test_act_backward(act, count, device):
     assert np.abs(got.cpu().double().numpy() - want).max() <= 1e-6
     inplace = up.to(device).clone()
     assert ops.act_backward_(inplace, y.to(device), act) is inplace and torch.equal(inplace, got)
+    if count % 4 == 0:                                      # `got` took 16-byte accesses: the 4-byte path gives the same bits
+        scalar = ops.act_backward_(_misaligned(up.to(device)), _misaligned(y.to(device)), act)
+        assert torch.equal(scalar, got)
 
 
 @pytest.mark.parametrize("act", ["elu", "tanh"])
@@ -94,6 +104,10 @@ def test_act_backward_on_a_misaligned_slice(act, device):
     assert gr.data_ptr() % 16 != 0
     model = R.elu_backward if act == "elu" else R.tanh_backward
     want = model(gr.cpu().double().numpy(), y.cpu().double().numpy())
+    # four of the 21-float channels are 84 floats: misaligned in place (4-byte path), 16-byte path on dense copies
+    y4, g4 = yb[:, 1:5], gb[:, 1:5]
+    assert torch.equal(ops.act_backward_(g4, y4, act, out=torch.empty((2, 4, 3, 7), device=device)),
+                       ops.act_backward_(g4.contiguous(), y4.contiguous(), act))
     ops.act_backward_(gr, y, act)
     assert np.abs(gr.cpu().double().numpy() - want).max() <= 1e-6
     assert torch.equal(gb[:, :1], keep[:, :1]) and torch.equal(gb[:, 4:], keep[:, 4:])
