@@ -328,6 +328,23 @@ __device__ __forceinline__ void zero_row_padding(float2 *buf, int lines, int pit
     }
 }
 
+// The walk of the LDS-engine row kernels over `lines` rows of w elements: load(l, j) -> Slot, then use(l, j, LDS index, slot).
+// Long rows take the structured walk (no per-element division), short ones the flat one.
+template <typename LoadF, typename UseF>
+__device__ __forceinline__ void walk_rows(int lines, int w, int pitch, LoadF load, UseF use) {
+    using namespace vfi::fft;
+    const float inv_w = 1.0f / (float)w;
+    if (w >= kThreads)
+        for_rows(lines, w, pitch, [&](int l, int j, int) { return load(l, j); },
+                 [&](int l, int j, int, int idx, const Slot &s) { use(l, j, idx, s); });
+    else
+        for_slots(lines * w, [&](int e) { const int l = fast_div(e, inv_w); return load(l, e - mul24(l, w)); },
+                  [&](int e, const Slot &s) {
+                      const int l = fast_div(e, inv_w), j = e - mul24(l, w);
+                      use(l, j, mul24(l, pitch) + phys(j), s);
+                  });
+}
+
 // rows of T -> inverse row FFT -> (phase, amplitude) or the complex coefficient (coeff_to_values, src/train/pyramid.py:63-69).
 // GRAD: the epilogue of the synthesis adjoint instead -- the coefficient gradient G and the forward's (p, A) at the same
 // offset give d phase = A (Im G cos p - Re G sin p), d amplitude = Re G cos p + Im G sin p.
@@ -342,8 +359,6 @@ __device__ __forceinline__ void rows_polar_body(const RowsArgsOf<GRAD> &a, const
     size_t *base = reinterpret_cast<size_t *>(twl + a.pw.tw_len);
     load_twiddles(twl, a.pw);
     line_bases(base, lines, row0, a.h, w, a.pm, NB);
-    const int total = lines * w;
-    const float inv_w = 1.0f / (float)w;
     constexpr bool blu = BLU;
     const float2 *Trow = a.T + row0 * w;
     auto fill_load = [&](int l, int j) {
@@ -384,25 +399,11 @@ __device__ __forceinline__ void rows_polar_body(const RowsArgsOf<GRAD> &a, const
             }
         }
     };
-    const bool wide = w >= kThreads;          // long rows: the structured walk (no per-element division)
-    if (wide)
-        for_rows(lines, w, pitch, [&](int l, int j, int) { return fill_load(l, j); },
-                 [&](int, int, int, int idx, const Slot &s) { fill_use(idx, s); });
-    else
-        for_slots(total, [&](int e) { const int l = fast_div(e, inv_w); return fill_load(l, e - mul24(l, w)); },
-                  [&](int e, const Slot &s) { const int l = fast_div(e, inv_w); fill_use(mul24(l, pitch) + phys(e - mul24(l, w)), s); });
+    walk_rows(lines, w, pitch, fill_load, [&](int, int, int idx, const Slot &s) { fill_use(idx, s); });
     if (blu) zero_row_padding(buf, lines, pitch, w, m);
     lds_barrier();
     fft_lines(buf, lines, pitch, a.pw, twl);
-    if (wide)
-        for_rows(lines, w, pitch, [&](int, int j, int) { return drain_load(j); },
-                 [&](int l, int j, int, int idx, const Slot &s) { drain_use(l, j, idx, s); });
-    else
-        for_slots(total, [&](int e) { return drain_load(e - mul24(fast_div(e, inv_w), w)); },
-                  [&](int e, const Slot &s) {
-                      const int l = fast_div(e, inv_w), j = e - mul24(l, w);
-                      drain_use(l, j, mul24(l, pitch) + phys(j), s);
-                  });
+    walk_rows(lines, w, pitch, [&](int, int j) { return drain_load(j); }, drain_use);
     if (want_max) {        // 64-lane butterfly, then one atomic per wave and group (amplitudes are >= 0: their bit patterns order like the values)
 #pragma unroll
         for (int t = 0; t < 4; ++t) {
@@ -455,8 +456,6 @@ __global__ __launch_bounds__(kThreads, kThreads / 128) void pyr_rows_from_polar_
     load_twiddles(twl, a.pw);
     line_bases(base, lines, row0, a.h, w, a.pm, NB);
     lds_barrier();
-    const int total = lines * w;
-    const float inv_w = 1.0f / (float)w;
     constexpr bool blu = BLU;
     auto fill_load = [&](int l, int j) {
         const size_t o = base[l] + j;
@@ -495,25 +494,11 @@ __global__ __launch_bounds__(kThreads, kThreads / 128) void pyr_rows_from_polar_
         return s;
     };
     auto drain_use = [&](int l, int j, int idx, const Slot &s) { Trow[mul24(l, w) + j] = store_value<false>(buf[idx], s.c, blu); };
-    const bool wide = w >= kThreads;
-    if (wide)
-        for_rows(lines, w, pitch, [&](int l, int j, int) { return fill_load(l, j); },
-                 [&](int, int j, int, int idx, const Slot &s) { fill_use(j, idx, s); });
-    else
-        for_slots(total, [&](int e) { const int l = fast_div(e, inv_w); return fill_load(l, e - mul24(l, w)); },
-                  [&](int e, const Slot &s) { const int l = fast_div(e, inv_w), j = e - mul24(l, w); fill_use(j, mul24(l, pitch) + phys(j), s); });
+    walk_rows(lines, w, pitch, fill_load, [&](int, int j, int idx, const Slot &s) { fill_use(j, idx, s); });
     if (blu) zero_row_padding(buf, lines, pitch, w, m);
     lds_barrier();
     fft_lines(buf, lines, pitch, a.pw, twl);
-    if (wide)
-        for_rows(lines, w, pitch, [&](int, int j, int) { return drain_load(j); },
-                 [&](int l, int j, int, int idx, const Slot &s) { drain_use(l, j, idx, s); });
-    else
-        for_slots(total, [&](int e) { return drain_load(e - mul24(fast_div(e, inv_w), w)); },
-                  [&](int e, const Slot &s) {
-                      const int l = fast_div(e, inv_w), j = e - mul24(l, w);
-                      drain_use(l, j, mul24(l, pitch) + phys(j), s);
-                  });
+    walk_rows(lines, w, pitch, [&](int, int j) { return drain_load(j); }, drain_use);
 }
 
 struct CombineColsArgs {

@@ -1,6 +1,6 @@
 // Internal interface between vfi_pyramid.hip (plans, level loop) and the pyramid's level kernels on the wave-private FFT
-// engine (vfi_wfft.h; kernels in vfi_pyrw_kernels.h, instantiated per engine length in vfi_pyrw_rows.hip /
-// vfi_pyrw_cols.hip).  Reference call sites: src/train/pyramid.py:35-46 (build / reconstruct), adapters :48-112.
+// engine (vfi_wfft.h; kernels in vfi_pyrw_kernels.h / vfi_pyrw_passes.h, instantiated per engine length in the
+// vfi_pyrw_*.hip files, one per pass).  Reference call sites: src/train/pyramid.py:35-46 (build / reconstruct), adapters :48-112.
 #pragma once
 #include "vfi_common.h"
 

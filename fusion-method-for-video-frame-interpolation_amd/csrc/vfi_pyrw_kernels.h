@@ -1,5 +1,5 @@
 // The steerable pyramid's level kernels on the wave-private FFT engine (vfi_wfft.h): templates over the engine
-// configuration, instantiated per engine length in vfi_pyrw_rows.hip / vfi_pyrw_cols.hip.
+// configuration, instantiated per engine length in the vfi_pyrw_*.hip files (one per pass, through vfi_pyrw_dispatch.h).
 //
 //   analysis  level k :  ana_cols  : (image, band, L adjacent columns) per wave: window_k of the R2C half spectrum S
 //                                    (Hermitian half expanded by index arithmetic) * Q_k[b] * i -> inverse column FFT -> T

@@ -1,62 +1,19 @@
 // Analysis row pass of the steerable pyramid on the wave-private FFT engine: rows_polar_kernel (vfi_pyrw_kernels.h)
 // instantiated for every row configuration of vfi_wfft_configs.h, plus the row-side lookups of vfi_pyramid_wave.h.
-#include "vfi_pyrw_kernels.h"
-
-#include <cmath>
+#include "vfi_pyrw_dispatch.h"
 
 namespace vfi {
 namespace pyrw {
 
-#define VFI_ROW_CFG(M, L, TEAM, PITCH, P0, P1, P2, R0, R1, R2, R3) Cfg<M, L, TEAM, false, PITCH, P0, P1, P2, R0, R1, R2, R3>
-
-namespace {
-template <class C>
-int polar_dispatch(const RowsArgs &a, hipStream_t s) {
-    const int nbatch = (a.planes * a.h + C::L - 1) / C::L;
-    if (a.tb.bluestein) {
-        if constexpr (blu_capable(C::M)) return launch_rows<C, true, rows_polar_kernel<C, true>>(a, nbatch, s);
-        return vfi::fail(VFI_ERR_UNSUPPORTED, "pyramid rows: engine length %d does not serve Bluestein", C::M);
-    }
-    return launch_rows<C, false, rows_polar_kernel<C, false>>(a, nbatch, s);
-}
-template <class C>
-int twiddles_of(float2 *out, int cap) {
-    if (C::TW > cap) return -1;
-    for_twiddles<C>([&](int idx, int e) {
-        const double ang = -2.0 * 3.14159265358979323846 * (double)e / (double)C::M;
-        out[idx] = make_float2((float)std::cos(ang), (float)std::sin(ang));
-    });
-    return C::TW;
-}
-}  // namespace
-
-int rows_engine_length(int n, int bluestein_m) {
-    const int m = bluestein_m ? bluestein_m : n;
-    if (bluestein_m && (!blu_capable(m) || 2 * n > m)) return 0;
-    switch (m) {
-#define X(M, L, TEAM, PITCH, P0, P1, P2, R0, R1, R2, R3) case M: return M;
-        VFI_WFFT_ROW_CONFIGS(X)
-#undef X
-    }
-    return 0;
-}
-
-int rows_twiddles(int M, float2 *out, int cap) {
-    switch (M) {
-#define X(M, L, TEAM, PITCH, P0, P1, P2, R0, R1, R2, R3) case M: return twiddles_of<VFI_ROW_CFG(M, L, TEAM, PITCH, P0, P1, P2, R0, R1, R2, R3)>(out, cap);
-        VFI_WFFT_ROW_CONFIGS(X)
-#undef X
-    }
-    return -1;
-}
+int rows_engine_length(int n, int bluestein_m) { return engine_length<kRowConfigs>(n, bluestein_m); }
+int rows_twiddles(int M, float2 *out, int cap) { return twiddles<kRowConfigs>(M, out, cap); }
 
 int launch_rows_polar(const RowsArgs &a, hipStream_t s) {
-    switch (a.tb.M) {
-#define X(M, L, TEAM, PITCH, P0, P1, P2, R0, R1, R2, R3) case M: return polar_dispatch<VFI_ROW_CFG(M, L, TEAM, PITCH, P0, P1, P2, R0, R1, R2, R3)>(a, s);
-        VFI_WFFT_ROW_CONFIGS(X)
-#undef X
-    }
-    return vfi::fail(VFI_ERR_UNSUPPORTED, "pyramid rows: no engine configuration for length %d", a.tb.M);
+    return dispatch<kRowConfigs>(a.tb, "pyramid rows", [&](auto c, auto blu) {
+        using C = typename decltype(c)::C;
+        constexpr bool BLU = decltype(blu)::value;
+        return launch_rows<C, BLU, rows_polar_kernel<C, BLU>>(a, (a.planes * a.h + C::L - 1) / C::L, s);
+    });
 }
 
 }  // namespace pyrw
