@@ -246,6 +246,214 @@ __global__ __launch_bounds__(kThreads) void head_reduce_kernel(const float *__re
     }
 }
 
+// ---- batch-statistics BatchNorm (block.py:17, nn.BatchNorm2d in training mode) ----------------------------------------
+// A channel's values are N runs of HW floats; as one line of N * HW elements it is cut into bn_blocks_per_channel equal
+// chunks (a multiple of 4 floats, so a 16-byte access never straddles two samples), one block each.  The cut depends on
+// (N, C, HW) alone and so does every order below.
+struct BnCut { int bpc; long long chunk; };
+inline BnCut bn_cut(int N, int C, int HW) {
+    const long long total = (long long)N * HW;
+    long long b = (total + 4095) / 4096;                // at least one unrolled trip of the block per chunk
+    const long long cap = VFI_REDUCE_WORKSPACE_FLOATS / (3ll * C);
+    b = b > cap ? cap : (b < 1 ? 1 : b);
+    BnCut c;
+    c.bpc = (int)b;
+    c.chunk = ((total + b - 1) / b + 3) / 4 * 4;
+    return c;
+}
+
+// Chan's merge of (na, ma, M2a) and (nb, mb, M2b); an empty side leaves the other as it is
+__device__ __forceinline__ void chan_merge(float &na, float &ma, float &qa, float nb, float mb, float qb) {
+    if (nb == 0.0f) return;
+    if (na == 0.0f) { na = nb; ma = mb; qa = qb; return; }
+    const float n = na + nb, d = mb - ma, r = nb / n;
+    ma = fmaf(d, r, ma);
+    qa = qa + qb + d * d * na * r;
+    na = n;
+}
+
+struct Welford {
+    float n, m, q;
+    // a group of 4: its own mean and M2 in two passes, then Chan's merge; 1 / n from v_rcp_f32 (1 ulp: the weight of a
+    // merge, not a term of the variance).  The first group is taken as it is, so a constant channel keeps its value exactly.
+    __device__ __forceinline__ void add(const float4 &v) {
+        const float gm = ((v.x + v.y) + (v.z + v.w)) * 0.25f;
+        const float a = v.x - gm, b = v.y - gm, c = v.z - gm, d = v.w - gm;
+        const float gq = (a * a + b * b) + (c * c + d * d);
+        const float nn = n + 4.0f, dl = gm - m, r = n == 0.0f ? 1.0f : 4.0f * __builtin_amdgcn_rcpf(nn);
+        m = fmaf(dl, r, m);
+        q = q + gq + dl * dl * n * r;
+        n = nn;
+    }
+    __device__ __forceinline__ void add(float v) {
+        const float nn = n + 1.0f, dl = v - m, r = n == 0.0f ? 1.0f : __builtin_amdgcn_rcpf(nn);
+        m = fmaf(dl, r, m);
+        q = fmaf(dl * dl * n, r, q);
+        n = nn;
+    }
+};
+
+// Walks elements [e0, e1) of channel c's line in steps of kThreads * L * U per block trip, sample by sample: f(ptr offset)
+// is called with the float offset of element (n, p) from the sample's channel base.
+template <typename T, typename BODY>
+__device__ __forceinline__ void bn_walk(long long e0, long long e1, int HW, BODY body) {
+    constexpr int L = sizeof(T) / sizeof(float);
+    while (e0 < e1) {
+        const int n = (int)(e0 / HW);
+        const int p0 = (int)(e0 - (long long)n * HW);
+        const long long rest = e1 - e0;
+        const int p1 = rest < HW - p0 ? p0 + (int)rest : HW;
+#pragma unroll 4
+        for (int p = p0 + (int)threadIdx.x * L; p < p1; p += kThreads * L) body(n, p);
+        e0 += p1 - p0;
+    }
+}
+
+// stage 1: block (b, c) writes (count, mean, M2) of its chunk of channel c
+template <typename T>
+__global__ __launch_bounds__(kThreads) void bn_stats_partial_kernel(const float *__restrict__ y, long long y_bs, int N, int HW,
+                                                                    long long chunk, float *__restrict__ part) {
+    __shared__ float lds[3 * kThreads];
+    const int c = blockIdx.y, b = blockIdx.x;
+    const long long total = (long long)N * HW;
+    const long long e0 = (long long)b * chunk, e1 = e0 + chunk < total ? e0 + chunk : total;
+    Welford w{0.0f, 0.0f, 0.0f};
+    const float *yc = y + (size_t)c * HW;
+    bn_walk<T>(e0, e1, HW, [&](int n, int p) { w.add(*reinterpret_cast<const T *>(yc + (size_t)n * y_bs + p)); });
+    const int t = threadIdx.x;
+    lds[t] = w.n; lds[kThreads + t] = w.m; lds[2 * kThreads + t] = w.q;
+    __syncthreads();
+    for (int s = kThreads / 2; s > 0; s >>= 1) {
+        if (t < s) chan_merge(lds[t], lds[kThreads + t], lds[2 * kThreads + t], lds[t + s], lds[kThreads + t + s], lds[2 * kThreads + t + s]);
+        __syncthreads();
+    }
+    if (t == 0) {
+        float *o = part + ((size_t)c * gridDim.x + b) * 3;
+        o[0] = lds[0]; o[1] = lds[kThreads]; o[2] = lds[2 * kThreads];
+    }
+}
+// stage 2: one block per channel merges its partials in block order
+__global__ void bn_stats_final_kernel(const float *__restrict__ part, int bpc, float *__restrict__ mean, float *__restrict__ var) {
+    if (threadIdx.x != 0) return;
+    const int c = blockIdx.x;
+    float n = 0.0f, m = 0.0f, q = 0.0f;
+    for (int b = 0; b < bpc; ++b) {
+        const float *o = part + ((size_t)c * bpc + b) * 3;
+        chan_merge(n, m, q, o[0], o[1], o[2]);
+    }
+    mean[c] = m;
+    var[c] = q / n;
+}
+
+__device__ __forceinline__ float bn_elu(float v) { return __builtin_amdgcn_fmed3f(v, __expf(v) - 1.0f, 0.0f); }   // apply_act's ELU
+
+// out = act(scale (y - mean) + beta), scale = gamma / sqrt(var + eps) formed once per block.  (y - mean) first: folded into
+// one shift, a channel with |mean| >> sigma would lose its digits in scale * y + shift.  out may be y itself.
+template <typename T, int ACT>
+__global__ __launch_bounds__(kThreads) void bn_act_forward_kernel(const float *y, long long y_bs, const float *__restrict__ mean,
+                                                                  const float *__restrict__ var, const float *__restrict__ gamma,
+                                                                  const float *__restrict__ beta, float eps, float *out,
+                                                                  long long o_bs, int C, int HW) {
+    constexpr int L = sizeof(T) / sizeof(float);
+    const int plane = blockIdx.y, n = plane / C, c = plane - n * C;
+    const float mu = mean[c], sc = gamma[c] * (1.0f / sqrtf(var[c] + eps)), sh = beta[c];
+    const float *yp = y + (size_t)n * y_bs + (size_t)c * HW;
+    float *op = out + (size_t)n * o_bs + (size_t)c * HW;
+    for (int p = (blockIdx.x * kThreads + threadIdx.x) * L; p < HW; p += gridDim.x * kThreads * L) {
+        const T v = *reinterpret_cast<const T *>(yp + p);
+        T r;
+#pragma unroll
+        for (int l = 0; l < L; ++l) {
+            const float z = fmaf(lane_get(v, l) - mu, sc, sh);
+            lane_set(r, l, ACT == VFI_ACT_ELU ? bn_elu(z) : z);
+        }
+        *reinterpret_cast<T *>(op + p) = r;
+    }
+}
+
+struct BnBackArgs {
+    const float *g_t, *t, *y, *mean, *var, *gamma;
+    long long gt_bs, t_bs, y_bs, gy_bs, chunk;
+    float *g_y, *g_gamma, *g_beta, *part;
+    float eps;
+    int N, C, HW, bpc;
+};
+template <int ACT> __device__ __forceinline__ float bn_gz(float g, float t) { return ACT == VFI_ACT_ELU ? (t > 0.0f ? g : g * (t + 1.0f)) : g; }
+
+// pass 1, stage 1: block (b, c) writes (sum g_z, sum g_z xhat) of its chunk
+template <typename T, int ACT>
+__global__ __launch_bounds__(kThreads) void bn_back_partial_kernel(BnBackArgs a) {
+    constexpr int L = sizeof(T) / sizeof(float);
+    __shared__ float lds[2 * kThreads];
+    const int c = blockIdx.y, b = blockIdx.x;
+    const long long total = (long long)a.N * a.HW;
+    const long long e0 = (long long)b * a.chunk, e1 = e0 + a.chunk < total ? e0 + a.chunk : total;
+    const float mu = a.mean[c], inv = 1.0f / sqrtf(a.var[c] + a.eps);
+    const size_t co = (size_t)c * a.HW;
+    float v[2] = {0.0f, 0.0f};
+    bn_walk<T>(e0, e1, a.HW, [&](int n, int p) {
+        const T g = *reinterpret_cast<const T *>(a.g_t + (size_t)n * a.gt_bs + co + p);
+        const T yv = *reinterpret_cast<const T *>(a.y + (size_t)n * a.y_bs + co + p);
+        T tv = g;
+        if (ACT == VFI_ACT_ELU) tv = *reinterpret_cast<const T *>(a.t + (size_t)n * a.t_bs + co + p);
+        float s0 = 0.0f, s1 = 0.0f;
+#pragma unroll
+        for (int l = 0; l < L; ++l) {
+            const float gz = bn_gz<ACT>(lane_get(g, l), lane_get(tv, l));
+            s0 += gz;
+            s1 = fmaf(gz, (lane_get(yv, l) - mu) * inv, s1);
+        }
+        v[0] += s0;
+        v[1] += s1;
+    });
+    block_sum<2>(v, lds);
+    if (threadIdx.x == 0) {
+        float *o = a.part + ((size_t)c * gridDim.x + b) * 2;
+        o[0] = v[0]; o[1] = v[1];
+    }
+}
+// pass 1, stage 2: one block per channel sums its partials in block order
+__global__ void bn_back_final_kernel(const float *__restrict__ part, int bpc, float *__restrict__ g_gamma, float *__restrict__ g_beta) {
+    if (threadIdx.x != 0) return;
+    const int c = blockIdx.x;
+    float s0 = 0.0f, s1 = 0.0f;
+    for (int b = 0; b < bpc; ++b) { s0 += part[((size_t)c * bpc + b) * 2]; s1 += part[((size_t)c * bpc + b) * 2 + 1]; }
+    g_beta[c] = s0;
+    g_gamma[c] = s1;
+}
+// pass 2: g_y = gamma inv (g_z - g_beta / n - xhat g_gamma / n); g_y may be g_t itself (every element is read, then
+// written, by one thread)
+template <typename T, int ACT>
+__global__ __launch_bounds__(kThreads) void bn_back_data_kernel(BnBackArgs a) {
+    constexpr int L = sizeof(T) / sizeof(float);
+    const int plane = blockIdx.y, n = plane / a.C, c = plane - n * a.C;
+    const float cnt = (float)((long long)a.N * a.HW);
+    const float mu = a.mean[c], inv = 1.0f / sqrtf(a.var[c] + a.eps), k = a.gamma[c] * inv;
+    const float mb = a.g_beta[c] / cnt, mg = a.g_gamma[c] / cnt;
+    const size_t co = (size_t)c * a.HW;
+    const float *gp = a.g_t + (size_t)n * a.gt_bs + co, *yp = a.y + (size_t)n * a.y_bs + co;
+    const float *tp = ACT == VFI_ACT_ELU ? a.t + (size_t)n * a.t_bs + co : gp;
+    float *op = a.g_y + (size_t)n * a.gy_bs + co;
+    for (int p = (blockIdx.x * kThreads + threadIdx.x) * L; p < a.HW; p += gridDim.x * kThreads * L) {
+        const T g = *reinterpret_cast<const T *>(gp + p), yv = *reinterpret_cast<const T *>(yp + p);
+        T tv = g, r;
+        if (ACT == VFI_ACT_ELU) tv = *reinterpret_cast<const T *>(tp + p);
+#pragma unroll
+        for (int l = 0; l < L; ++l) {
+            const float gz = bn_gz<ACT>(lane_get(g, l), lane_get(tv, l));
+            const float xh = (lane_get(yv, l) - mu) * inv;
+            lane_set(r, l, k * ((gz - mb) - xh * mg));
+        }
+        *reinterpret_cast<T *>(op + p) = r;
+    }
+}
+
+// grid of the two per-plane passes: x over a plane's pixels (up to 64 blocks of one 4-deep trip each), y = N * C planes
+inline dim3 bn_plane_grid(int N, int C, int HW, int lanes) {
+    long long bx = ((long long)HW + (long long)kThreads * lanes * 4 - 1) / ((long long)kThreads * lanes * 4);
+    return dim3((unsigned)(bx > 64 ? 64 : bx), (unsigned)(N * C));
+}
+
 }  // namespace
 
 extern "C" int vfi_resize_bilinear_adjoint(const float *grad_y, long long gy_bstride, float *grad_x, long long gx_bstride,
@@ -343,4 +551,75 @@ extern "C" int vfi_l1_backward(const float *a, const float *b, const float *upst
     if (wrap) LAUNCH_1D(sum_backward_kernel<AbsTerm<true>>, count, stream, AbsTerm<true>{}, a, b, upstream, grad_a, grad_b, count, factor);
     else LAUNCH_1D(sum_backward_kernel<AbsTerm<false>>, count, stream, AbsTerm<false>{}, a, b, upstream, grad_a, grad_b, count, factor);
     return vfi::check_launch("vfi_l1_backward");
+}
+
+extern "C" int vfi_bn_stats(const float *y, long long y_bstride, int N, int C, int HW, float *mean, float *var, float *workspace,
+                            vfi_stream_t stream) {
+    VFI_REQUIRE(y && mean && var && workspace, VFI_ERR_INVALID_ARG, "vfi_bn_stats: null pointer");
+    VFI_REQUIRE(N > 0 && C > 0 && HW > 0, VFI_ERR_INVALID_ARG, "vfi_bn_stats: bad sizes");
+    VFI_REQUIRE((long long)N * HW >= 2, VFI_ERR_SHAPE, "vfi_bn_stats: expected more than 1 value per channel (N * HW = %lld)", (long long)N * HW);
+    VFI_REQUIRE(C <= 65535 && 3ll * C <= VFI_REDUCE_WORKSPACE_FLOATS && HW < (1 << 30) && (long long)N * HW < (1ll << 40) && (long long)C * HW < (1ll << 40),
+                VFI_ERR_UNSUPPORTED, "vfi_bn_stats: C = %d, N * HW = %lld beyond the workspace or the grid", C, (long long)N * HW);
+    const BnCut cut = bn_cut(N, C, HW);
+    const bool v4 = HW % 4 == 0 && y_bstride % 4 == 0 && aligned16(y);
+    hipStream_t s = vfi::as_stream(stream);
+    const dim3 grid(cut.bpc, C);
+    if (v4) hipLaunchKernelGGL(bn_stats_partial_kernel<float4>, grid, dim3(kThreads), 0, s, y, y_bstride, N, HW, cut.chunk, workspace);
+    else hipLaunchKernelGGL(bn_stats_partial_kernel<float>, grid, dim3(kThreads), 0, s, y, y_bstride, N, HW, cut.chunk, workspace);
+    hipLaunchKernelGGL(bn_stats_final_kernel, dim3(C), dim3(64), 0, s, workspace, cut.bpc, mean, var);
+    return vfi::check_launch("vfi_bn_stats");
+}
+
+extern "C" int vfi_bn_act_forward(const float *y, long long y_bstride, const float *mean, const float *var, const float *gamma,
+                                  const float *beta, float eps, int act, float *out, long long out_bstride, int N, int C, int HW,
+                                  vfi_stream_t stream) {
+    VFI_REQUIRE(y && mean && var && gamma && beta && out, VFI_ERR_INVALID_ARG, "vfi_bn_act_forward: null pointer");
+    VFI_REQUIRE(N > 0 && C > 0 && HW > 0 && eps >= 0.0f, VFI_ERR_INVALID_ARG, "vfi_bn_act_forward: bad sizes");
+    VFI_REQUIRE(act == VFI_ACT_NONE || act == VFI_ACT_ELU, VFI_ERR_UNSUPPORTED, "vfi_bn_act_forward: act %d (none and ELU only)", act);
+    VFI_REQUIRE((long long)N * C <= 65535 && HW < (1 << 30), VFI_ERR_UNSUPPORTED, "vfi_bn_act_forward: N * C = %lld planes, HW = %d beyond the grid", (long long)N * C, HW);
+    const bool v4 = HW % 4 == 0 && y_bstride % 4 == 0 && out_bstride % 4 == 0 && aligned16(y) && aligned16(out);
+    hipStream_t s = vfi::as_stream(stream);
+    const dim3 grid = bn_plane_grid(N, C, HW, v4 ? 4 : 1);
+#define VFI_BN_FWD(T, ACT) \
+    hipLaunchKernelGGL((bn_act_forward_kernel<T, ACT>), grid, dim3(kThreads), 0, s, y, y_bstride, mean, var, gamma, beta, eps, out, out_bstride, C, HW)
+    if (act == VFI_ACT_ELU) { if (v4) VFI_BN_FWD(float4, VFI_ACT_ELU); else VFI_BN_FWD(float, VFI_ACT_ELU); }
+    else { if (v4) VFI_BN_FWD(float4, VFI_ACT_NONE); else VFI_BN_FWD(float, VFI_ACT_NONE); }
+#undef VFI_BN_FWD
+    return vfi::check_launch("vfi_bn_act_forward");
+}
+
+extern "C" int vfi_bn_act_backward(const float *g_t, long long gt_bstride, const float *t, long long t_bstride, const float *y,
+                                   long long y_bstride, const float *mean, const float *var, const float *gamma, float eps, int act,
+                                   float *g_y, long long gy_bstride, float *g_gamma, float *g_beta, float *workspace, int N, int C,
+                                   int HW, vfi_stream_t stream) {
+    VFI_REQUIRE(g_t && y && mean && var && g_gamma && g_beta && workspace, VFI_ERR_INVALID_ARG, "vfi_bn_act_backward: null pointer");
+    VFI_REQUIRE(act == VFI_ACT_NONE || act == VFI_ACT_ELU, VFI_ERR_UNSUPPORTED, "vfi_bn_act_backward: act %d (none and ELU only)", act);
+    VFI_REQUIRE(act == VFI_ACT_NONE || t, VFI_ERR_INVALID_ARG, "vfi_bn_act_backward: ELU needs its output t");
+    VFI_REQUIRE(!g_y || gamma, VFI_ERR_INVALID_ARG, "vfi_bn_act_backward: g_y needs gamma");
+    VFI_REQUIRE(N > 0 && C > 0 && HW > 0 && eps >= 0.0f, VFI_ERR_INVALID_ARG, "vfi_bn_act_backward: bad sizes");
+    VFI_REQUIRE(C <= 65535 && 3ll * C <= VFI_REDUCE_WORKSPACE_FLOATS && (long long)N * C <= 65535 && HW < (1 << 30) && (long long)N * HW < (1ll << 40) &&
+                (long long)C * HW < (1ll << 40), VFI_ERR_UNSUPPORTED, "vfi_bn_act_backward: N = %d, C = %d, HW = %d beyond the workspace or the grid", N, C, HW);
+    const BnCut cut = bn_cut(N, C, HW);
+    BnBackArgs a{};
+    a.g_t = g_t; a.t = t; a.y = y; a.mean = mean; a.var = var; a.gamma = gamma; a.gt_bs = gt_bstride; a.t_bs = t_bstride;
+    a.y_bs = y_bstride; a.gy_bs = gy_bstride; a.chunk = cut.chunk; a.g_y = g_y; a.g_gamma = g_gamma; a.g_beta = g_beta;
+    a.part = workspace; a.eps = eps; a.N = N; a.C = C; a.HW = HW; a.bpc = cut.bpc;
+    const bool elu = act == VFI_ACT_ELU;
+    const bool v4 = HW % 4 == 0 && gt_bstride % 4 == 0 && y_bstride % 4 == 0 && aligned16(g_t) && aligned16(y) &&
+                    (!elu || (t_bstride % 4 == 0 && aligned16(t))) && (!g_y || (gy_bstride % 4 == 0 && aligned16(g_y)));
+    hipStream_t s = vfi::as_stream(stream);
+    const dim3 rgrid(cut.bpc, C);
+    if (elu) { if (v4) hipLaunchKernelGGL((bn_back_partial_kernel<float4, VFI_ACT_ELU>), rgrid, dim3(kThreads), 0, s, a);
+               else hipLaunchKernelGGL((bn_back_partial_kernel<float, VFI_ACT_ELU>), rgrid, dim3(kThreads), 0, s, a); }
+    else { if (v4) hipLaunchKernelGGL((bn_back_partial_kernel<float4, VFI_ACT_NONE>), rgrid, dim3(kThreads), 0, s, a);
+           else hipLaunchKernelGGL((bn_back_partial_kernel<float, VFI_ACT_NONE>), rgrid, dim3(kThreads), 0, s, a); }
+    hipLaunchKernelGGL(bn_back_final_kernel, dim3(C), dim3(64), 0, s, workspace, cut.bpc, g_gamma, g_beta);
+    if (g_y) {
+        const dim3 grid = bn_plane_grid(N, C, HW, v4 ? 4 : 1);
+        if (elu) { if (v4) hipLaunchKernelGGL((bn_back_data_kernel<float4, VFI_ACT_ELU>), grid, dim3(kThreads), 0, s, a);
+                   else hipLaunchKernelGGL((bn_back_data_kernel<float, VFI_ACT_ELU>), grid, dim3(kThreads), 0, s, a); }
+        else { if (v4) hipLaunchKernelGGL((bn_back_data_kernel<float4, VFI_ACT_NONE>), grid, dim3(kThreads), 0, s, a);
+               else hipLaunchKernelGGL((bn_back_data_kernel<float, VFI_ACT_NONE>), grid, dim3(kThreads), 0, s, a); }
+    }
+    return vfi::check_launch("vfi_bn_act_backward");
 }

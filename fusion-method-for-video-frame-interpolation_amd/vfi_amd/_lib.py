@@ -96,6 +96,9 @@ SIGNATURES = {
     "vfi_phasenet_emit_backward": [c_f, c_f, c_f, c_l, c_f, c_f, c_l, c_i, c_i, c_s],
     "vfi_phasenet_emit_low_backward": [c_f, c_f, c_l, c_f, c_f, c_l, c_i, c_i, c_s],
     "vfi_phasenet_predict_backward": [c_f, c_l] * 3 + [c_f] * 5 + [c_l, c_f, c_l, c_f, c_f, c_f, c_i, c_i, c_s],
+    "vfi_bn_stats": [c_f, c_l, c_i, c_i, c_i, c_f, c_f, c_f, c_s],
+    "vfi_bn_act_forward": [c_f, c_l, c_f, c_f, c_f, c_f, c_fl, c_i, c_f, c_l, c_i, c_i, c_i, c_s],
+    "vfi_bn_act_backward": [c_f, c_l] * 3 + [c_f, c_f, c_f, c_fl, c_i, c_f, c_l, c_f, c_f, c_f, c_i, c_i, c_i, c_s],
     "vfi_l1_forward": [c_f, c_f, c_l, c_i, c_fl, c_f, c_f, c_s],
     "vfi_l1_backward": [c_f] * 5 + [c_l, c_i, c_fl, c_s],
 }

@@ -28,7 +28,8 @@ class ConvParams(nn.Module):
 
 
 class BatchNormParams(nn.Module):
-    """Parameters/buffers of nn.BatchNorm2d (eval mode only; folded into the preceding conv)."""
+    """Parameters/buffers of nn.BatchNorm2d (the module is always in eval mode; folded into the preceding conv, or run on
+    batch statistics by vfi_amd.phase_net.grad)."""
 
     def __init__(self, c, eps=1e-5):
         super().__init__()
@@ -68,9 +69,10 @@ class PackedModule(nn.Module):
         self._packed_key = None
 
     def _param_key(self):
-        """The parameters' identities and in-place version counters: an optimiser step (or any in-place write) bumps
-        `_version`, so the cache notices it without a hook."""
-        return tuple((id(p), p._version) for p in self.parameters())
+        """The parameters' and buffers' identities and in-place version counters: an optimiser step (or any in-place write)
+        bumps `_version`, so the cache notices it without a hook.  The buffers count because packs fold BatchNorm's running
+        statistics, which a batch-statistics forward moves without touching a parameter; inference never writes them."""
+        return tuple((id(p), p._version) for p in (*self.parameters(), *self.buffers()))
 
     def load_state_dict(self, *a, **k):
         r = super().load_state_dict(*a, **k)

@@ -639,6 +639,71 @@ def phasenet_predict_backward(feat, pred, amp_in, max_amp, weight, grad_phase=No
     return gf, gw, gb
 
 
+# ---- batch-statistics BatchNorm of a PhaseNet block ----------------------------------------------
+def _channel_vec(t, c, name):
+    if t.numel() != c:
+        raise VfiLibraryError(f"{name} must hold {c} floats, got {tuple(t.shape)}")
+    return _lib.dptr(t.detach(), name)
+
+
+def bn_stats(y):
+    """Per-channel (mean, biased variance) of y (N,C,H,W; may be a channel slice) over samples and pixels (vfi_bn_stats):
+    nn.BatchNorm2d's batch statistics.  One value per channel raises ValueError, as torch does."""
+    n, c, h, w = y.shape
+    if n * h * w < 2:
+        raise ValueError(f"Expected more than 1 value per channel when training, got input size {tuple(y.shape)}")
+    yp, ys = _slice_ptr(y, "y")
+    mean, var = new((c,), y), new((c,), y)
+    _lib.call("vfi_bn_stats", yp, ys, n, c, h * w, mean.data_ptr(), var.data_ptr(), _reduce_workspace(y).data_ptr(),
+              _lib.stream_ptr(), work=_prof("byte", 4.0 * n * c * h * w, "bn_stats"))
+    return mean, var
+
+
+def bn_act_forward(y, mean, var, gamma, beta, eps, act="elu", out=None):
+    """act(gamma (y - mean) / sqrt(var + eps) + beta), act in None | 'elu' (vfi_bn_act_forward); y and out may be channel
+    slices, out may be y."""
+    n, c, h, w = y.shape
+    if act not in (None, "none", "elu"):
+        raise VfiLibraryError(f"bn_act_forward: activation {act!r} (none and elu only)")
+    if out is None:
+        out = new((n, c, h, w), y)
+    elif tuple(out.shape) != (n, c, h, w):
+        raise VfiLibraryError(f"bn_act_forward: out shape {tuple(out.shape)} != {(n, c, h, w)}")
+    yp, ys = _slice_ptr(y, "y")
+    op, os_ = _slice_ptr(out, "out")
+    _lib.call("vfi_bn_act_forward", yp, ys, _channel_vec(mean, c, "mean"), _channel_vec(var, c, "var"),
+              _channel_vec(gamma, c, "gamma"), _channel_vec(beta, c, "beta"), float(eps), ACT[act], op, os_, n, c, h * w,
+              _lib.stream_ptr(), work=_prof("byte", 8.0 * n * c * h * w, "bn_act_forward"))
+    return out
+
+
+def bn_act_backward(g_t, t, y, mean, var, gamma, eps, act="elu", need_data=True, out=None):
+    """Adjoint of bn_stats + bn_act_forward (vfi_bn_act_backward) -> (g_y or None, g_gamma (C,), g_beta (C,)).  g_t, t, y may
+    be channel slices; t is the forward's output (None without an activation).  `out`: where g_y goes, g_t itself is fine;
+    need_data=False skips g_y."""
+    n, c, h, w = g_t.shape
+    if act not in (None, "none", "elu"):
+        raise VfiLibraryError(f"bn_act_backward: activation {act!r} (none and elu only)")
+    elu = act == "elu"
+    if tuple(y.shape) != (n, c, h, w) or (elu and (t is None or tuple(t.shape) != (n, c, h, w))):
+        raise VfiLibraryError("bn_act_backward: shape mismatch")
+    gp, gs = _slice_ptr(g_t, "g_t")
+    tp, ts = _slice_ptr(t, "t") if elu else (None, 0)
+    yp, ys = _slice_ptr(y, "y")
+    g_y = None
+    if need_data:
+        g_y = new((n, c, h, w), g_t) if out is None else out
+        if tuple(g_y.shape) != (n, c, h, w):
+            raise VfiLibraryError(f"bn_act_backward: out shape {tuple(g_y.shape)} != {(n, c, h, w)}")
+    op, os_ = (None, 0) if g_y is None else _slice_ptr(g_y, "out")
+    g_gamma, g_beta = new((c,), g_t), new((c,), g_t)
+    _lib.call("vfi_bn_act_backward", gp, gs, tp, ts, yp, ys, _channel_vec(mean, c, "mean"), _channel_vec(var, c, "var"),
+              _channel_vec(gamma, c, "gamma"), float(eps), ACT[act], op, os_, g_gamma.data_ptr(), g_beta.data_ptr(),
+              _reduce_workspace(g_t).data_ptr(), n, c, h * w, _lib.stream_ptr(),
+              work=_prof("byte", 4.0 * n * c * h * w * ((2 + elu) * (1 + need_data) + need_data), "bn_act_backward"))
+    return g_y, g_gamma, g_beta
+
+
 def phasenet_emit_low(pred, low_in, max_low):
     """The low level's output (vfi_phasenet_emit_low): pred (N,1,H,W), low_in (N,2,H,W) normalised, max_low (N,) -> (N,1,H,W)."""
     n, c, h, w = pred.shape

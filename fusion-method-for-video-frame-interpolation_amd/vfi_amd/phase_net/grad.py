@@ -13,6 +13,10 @@ The walk's own pieces, one band level (phase_net.py:138-168):
     x = level_input(f, c, phase, amp)                 # both resizes and the concatenation, written into one buffer
     f = block_features(blk, x)                        # conv 1 + folded BN + ELU + conv 2 + ELU
     c, phase_out, amp_out = level_head(blk, f, amp, max_amp)      # vfi_phasenet_predict / vfi_phasenet_predict_backward
+
+A block whose `batch_stats` flag is set (PhaseNetBlock.batch_statistics, PhaseNet.fine_tune(batch_stats=True)) takes the
+batch-statistics route of section 17 in the same nodes: conv 1 with its raw weights, vfi_bn_stats, vfi_bn_act_forward, conv 2,
+and the running statistics updated at every forward, grad mode or not.  With the flag off nothing here changes.
 """
 import torch
 
@@ -60,6 +64,68 @@ def block_packs_transposed(blk):
     return cache["T"]
 
 
+BN_MOMENTUM = 0.1      # nn.BatchNorm2d's default, which block.py:17 takes
+
+
+def block_packs_raw(blk):
+    """The batch-statistics route's packs: (conv 1 with its RAW weights and bias, conv 2, prediction map), and under "T" their
+    transposed packs once a backward asked for them.  A cache of its own beside block_packs', keyed on the six convolution
+    tensors alone: this route rewrites the running statistics at every forward, and a key that held them would rebuild
+    every pack (and wait for the stream) at every level."""
+    fm, pm = blk.feature_map, blk.prediction_map
+    tensors = [fm[0].weight, fm[0].bias, fm[3].weight, fm[3].bias, pm[0].weight, pm[0].bias]
+    key = tuple((id(t), t._version, t.device) for t in tensors)
+    cache = blk.__dict__.get("_vfi_packs_raw")
+    if cache is None or cache["key"] != key:
+        with torch.no_grad():
+            cache = {"key": key, "fwd": tuple(ops.PackedConv(tensors[i], tensors[i + 1]) for i in (0, 2, 4))}
+        blk.__dict__["_vfi_packs_raw"] = cache
+        torch.cuda.current_stream(fm[0].weight.device).synchronize()
+    return cache
+
+
+def block_packs_raw_transposed(blk):
+    cache = block_packs_raw(blk)
+    if "T" not in cache:
+        fm, pm = blk.feature_map, blk.prediction_map
+        with torch.no_grad():
+            cache["T"] = tuple(ops.packed_transposed(m.weight) for m in (fm[0], fm[3], pm[0]))
+        torch.cuda.current_stream(fm[0].weight.device).synchronize()
+    return cache["T"]
+
+
+def _forward_packs(blk):
+    return (block_packs_raw(blk) if blk.batch_stats else block_packs(blk))["fwd"]
+
+
+def bn_feature_launches(blk, x):
+    """The feature part on batch statistics (block.py:15-21 in training mode) -> (y, t, f, mean, var): conv 1 with its raw
+    weights and no activation, the batch's statistics, normalise + ELU, conv 2; then the running statistics move as
+    nn.BatchNorm2d's do (momentum 0.1, unbiased variance), in place, so that their version counters move too."""
+    c1, c2 = block_packs_raw(blk)["fwd"][:2]
+    bn = blk.feature_map[1]
+    mode = "reflect" if c1.ks == 3 else "zeros"
+    y = ops.conv2d(x, c1, mode, None)
+    mean, var = ops.bn_stats(y)
+    t = ops.bn_act_forward(y, mean, var, bn.weight, bn.bias, bn.eps, "elu")
+    f = ops.conv2d(t, c2, mode, "elu")
+    n = y.shape[0] * y.shape[2] * y.shape[3]
+    with torch.no_grad():
+        bn.running_mean.mul_(1.0 - BN_MOMENTUM).add_(mean, alpha=BN_MOMENTUM)
+        bn.running_var.mul_(1.0 - BN_MOMENTUM).add_(var, alpha=BN_MOMENTUM * n / (n - 1))
+        bn.num_batches_tracked.add_(1)
+    return y, t, f, mean, var
+
+
+def _feature_forward(blk, x):
+    """-> (t, f, bn): bn = (y, mean, var) on the batch-statistics route, None on the running statistics."""
+    if blk.batch_stats:
+        y, t, f, mean, var = bn_feature_launches(blk, x)
+        return t, f, (y, mean, var)
+    t, f = feature_launches(block_packs(blk)["fwd"], x)
+    return t, f, None
+
+
 def block_launches(packs, x):
     """The block's three launches (BN folded, ELU / tanh in the epilogues, reflect padding for 3x3) -> (t, f, c), t the
     post-ELU output of conv 1."""
@@ -87,12 +153,16 @@ def _feature_params(blk):
 
 
 def block_forward(blk, x):
-    """PhaseNetBlock.forward: (f, c) = (feature_map(x), prediction_map(f)) with BN on its running statistics."""
+    """PhaseNetBlock.forward: (f, c) = (feature_map(x), prediction_map(f)) with BN on its running statistics, or on the
+    batch's when blk.batch_stats is set."""
     _check_eval(blk)
     pm = blk.prediction_map
     params = (*_feature_params(blk), pm[0].weight, pm[0].bias)
     if _wants_grad(x, *params):
         return _BlockFunction.apply(blk, x, *params)
+    if blk.batch_stats:
+        _, f, _ = _feature_forward(blk, x)
+        return f, ops.conv2d(f, block_packs_raw(blk)["fwd"][2], "zeros", "tanh")
     _, f, c = block_launches(block_packs(blk)["fwd"], x)
     return f, c
 
@@ -101,11 +171,17 @@ class _BlockFunction(torch.autograd.Function):
     """One PhaseNet block as one autograd node.  Inputs: (blk, x, then w1, b1, gamma, beta, w2, b2, wp, bp).  The forward
     runs exactly the inference launches and keeps t (post-ELU conv 1), f and c.  Backward: tanh backward -> 1x1 weight and
     data gradient -> + g_f -> ELU backward on f -> conv 2 weight and data gradient -> ELU backward on t -> conv 1 weight
-    gradient (data gradient only when x needs one) -> the folded BatchNorm unfolded on parameter-sized tensors."""
+    gradient (data gradient only when x needs one) -> the folded BatchNorm unfolded on parameter-sized tensors.  On the
+    batch-statistics route the node also keeps (y, mean, var), and _features_backward takes vfi_bn_act_backward."""
 
     @staticmethod
     def forward(ctx, blk, x, *params):
-        t, f, c = block_launches(block_packs(blk)["fwd"], x)
+        if blk.batch_stats:
+            t, f, ctx.bn = _feature_forward(blk, x)
+            c = ops.conv2d(f, block_packs_raw(blk)["fwd"][2], "zeros", "tanh")
+        else:
+            t, f, c = block_launches(block_packs(blk)["fwd"], x)
+            ctx.bn = None
         ctx.blk, ctx.t = blk, t
         ctx.save_for_backward(x, f, c, *params)       # in-place changes between forward and backward raise
         ctx.set_materialize_grads(False)
@@ -116,7 +192,7 @@ class _BlockFunction(torch.autograd.Function):
         blk, t = ctx.blk, ctx.t
         x, f, c = ctx.saved_tensors[:3]
         need = ctx.needs_input_grad             # (blk, x, w1, b1, gamma, beta, w2, b2, wp, bp)
-        pTp = block_packs_transposed(blk)[2]
+        pTp = (block_packs_raw_transposed(blk) if ctx.bn is not None else block_packs_transposed(blk))[2]
         grads = [None] * 8
         first = any(need[2:6])                      # conv 1 or its BatchNorm
         below = first or need[1] or need[6] or need[7]      # anything under the prediction map
@@ -131,21 +207,23 @@ class _BlockFunction(torch.autograd.Function):
         elif g is not None and below:
             g = g.clone()
         if g is None or not below:
-            ctx.t = None
+            ctx.t = ctx.bn = None
             return (None, None, *[gp if need[2 + j] else None for j, gp in enumerate(grads)])
-        gx, grads[:6] = _features_backward(blk, x, t, f, g, need[1:8])
+        gx, grads[:6] = _features_backward(blk, x, t, f, g, need[1:8], ctx.bn)
         grads = [gp if need[2 + j] else None for j, gp in enumerate(grads)]
-        ctx.t = None
+        ctx.t = ctx.bn = None
         return (None, gx, *grads)
 
 
-def _features_backward(blk, x, t, f, g, need):
+def _features_backward(blk, x, t, f, g, need, bn=None):
     """The walk below the head, shared by the block node and the feature node: g, the gradient of f, is the caller's own
-    tensor and is overwritten (ELU backward in place).  need = (x, w1, b1, gamma, beta, w2, b2) -> (gx, six gradients)."""
+    tensor and is overwritten (ELU backward in place).  need = (x, w1, b1, gamma, beta, w2, b2) -> (gx, six gradients).
+    bn = (y, mean, var) of a batch-statistics forward: below g_t the BatchNorm's own adjoint (vfi_bn_act_backward, in place
+    on g_t) gives g_y, g_gamma and g_beta, and conv 1's gradients come from g_y with the raw weights -- nothing to unfold."""
     fm = blk.feature_map
     ks = fm[0].weight.shape[2]
     mode = "reflect" if ks == 3 else "zeros"
-    pT1, pT2, _ = block_packs_transposed(blk)
+    pT1, pT2, _ = block_packs_transposed(blk) if bn is None else block_packs_raw_transposed(blk)
     grads = [None] * 6
     first = any(need[1:5])                      # conv 1 or its BatchNorm
     ops.act_backward_(g, f, "elu")
@@ -154,6 +232,16 @@ def _features_backward(blk, x, t, f, g, need):
     gx = None
     if first or need[0]:
         g_t = ops.conv2d_backward_data(g, pT2, mode)
+        if bn is not None:
+            y, mean, var = bn
+            conv1 = need[1] or need[2]
+            g_y, grads[2], grads[3] = ops.bn_act_backward(g_t, t, y, mean, var, fm[1].weight, fm[1].eps, "elu",
+                                                          need_data=bool(conv1 or need[0]), out=g_t)
+            if conv1:
+                grads[0], grads[1] = ops.conv2d_backward_weight(x, g_y, ks, mode, bias=bool(need[2]))
+            if need[0]:
+                gx = ops.conv2d_backward_data(g_y, pT1, mode)
+            return gx, grads
         ops.act_backward_(g_t, t, "elu")
         if first:
             g_wf, g_bf = ops.conv2d_backward_weight(x, g_t, ks, mode, bias=True)
@@ -173,13 +261,13 @@ def _features_backward(blk, x, t, f, g, need):
 
 # ---- the walk's nodes: feature part, head, level input -----------------------------------------------------------------
 def block_features(blk, x):
-    """f = blk.feature_map(x) (conv 1 + BatchNorm on its running statistics + ELU + conv 2 + ELU), x in the reference's
-    channel order; an autograd node when x or a feature parameter requires grad."""
+    """f = blk.feature_map(x) (conv 1 + BatchNorm on its running statistics, or the batch's when blk.batch_stats is set, + ELU
+    + conv 2 + ELU), x in the reference's channel order; an autograd node when x or a feature parameter requires grad."""
     _check_eval(blk)
     params = _feature_params(blk)
     if _wants_grad(x, *params):
         return _FeatureFunction.apply(blk, x, *params)
-    return feature_launches(block_packs(blk)["fwd"], x)[1]
+    return _feature_forward(blk, x)[1]
 
 
 class _FeatureFunction(torch.autograd.Function):
@@ -187,7 +275,7 @@ class _FeatureFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, blk, x, *params):
-        t, f = feature_launches(block_packs(blk)["fwd"], x)
+        t, f, ctx.bn = _feature_forward(blk, x)
         ctx.blk, ctx.t = blk, t
         ctx.save_for_backward(x, f, *params)
         return f
@@ -196,8 +284,8 @@ class _FeatureFunction(torch.autograd.Function):
     def backward(ctx, g_f):
         x, f = ctx.saved_tensors[:2]
         need = ctx.needs_input_grad             # (blk, x, w1, b1, gamma, beta, w2, b2)
-        gx, grads = _features_backward(ctx.blk, x, ctx.t, f, g_f.contiguous().clone(), need[1:8])
-        ctx.t = None
+        gx, grads = _features_backward(ctx.blk, x, ctx.t, f, g_f.contiguous().clone(), need[1:8], ctx.bn)
+        ctx.t = ctx.bn = None
         return (None, gx, *[gp if need[2 + j] else None for j, gp in enumerate(grads)])
 
 
@@ -229,7 +317,7 @@ def level_head(blk, f, amp_in, max_amp):
     pm = blk.prediction_map[0]
     if _wants_grad(f, pm.weight, pm.bias):
         return _HeadFunction.apply(blk, f, amp_in.detach(), max_amp.detach(), pm.weight, pm.bias)
-    return ops.phasenet_predict(f, block_packs(blk)["fwd"][2], amp_in, max_amp)
+    return ops.phasenet_predict(f, _forward_packs(blk)[2], amp_in, max_amp)
 
 
 class _HeadFunction(torch.autograd.Function):
@@ -238,7 +326,7 @@ class _HeadFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, blk, f, amp_in, max_amp, wp, bp):
-        c, phase, amp = ops.phasenet_predict(f, block_packs(blk)["fwd"][2], amp_in, max_amp)
+        c, phase, amp = ops.phasenet_predict(f, _forward_packs(blk)[2], amp_in, max_amp)
         ctx.save_for_backward(f, c, amp_in, max_amp, wp)
         ctx.set_materialize_grads(False)
         return c, phase, amp

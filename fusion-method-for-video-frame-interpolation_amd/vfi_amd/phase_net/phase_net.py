@@ -15,7 +15,8 @@ Maxima are returned/kept per call on the module (as the reference does, phase_ne
 
 After `fine_tune()`, with grad mode on and a parameter of `layers` requiring grad, `forward` takes a second route,
 `_forward_grad`: the same walk as an autograd graph with HIP backward kernels, BatchNorm on its running statistics (DESIGN.md
-section 16).  Every other call runs the code above, unchanged.
+section 16).  After `fine_tune(batch_stats=True)` every forward takes that route, with BatchNorm on the batch's statistics
+and the running statistics updated (training from scratch, section 17).  Every other call runs the code above, unchanged.
 """
 import math
 
@@ -30,7 +31,9 @@ class PhaseNetBlock(torch.nn.Module):
     """The reference's block with its key names (phase_net.py:179-207, block.py:4-32).  PhaseNet.forward runs the blocks
     through its own permuted packs; `forward` here is the reference's `(f, c) = block(x)` on an input in the reference's
     channel order, differentiable with a HIP backward.  BatchNorm uses its running statistics: a new
-    block is in eval mode, and a block switched to training mode refuses to run (batch statistics are not built)."""
+    block is in eval mode, and a block switched to training mode refuses to run.  Batch statistics are asked for with
+    `batch_statistics()` (or the network's `fine_tune(batch_stats=True)`), not with `train(True)`: the block stays in eval
+    mode (`training` is False) and its flag `batch_stats` selects the route of DESIGN.md section 17."""
 
     def __init__(self, c_in, c_out, pred_out, kernel_size, device=None, dropout=0.5):
         super().__init__()
@@ -38,9 +41,18 @@ class PhaseNetBlock(torch.nn.Module):
         self.feature_map = Indexed({0: ConvParams(c_in, c_out, k), 1: BatchNormParams(c_out),
                                     3: ConvParams(c_out, c_out, k)})
         self.prediction_map = Indexed({0: ConvParams(c_out, pred_out, 1)})
+        self.batch_stats = False
         self.train(False)
         if device is not None:
             self.to(device)
+
+    def batch_statistics(self, mode=True):
+        """BatchNorm on the batch's statistics on or off (off in a new block), for a block used on its own.  With it on,
+        every forward -- grad mode or not -- normalises with the mean and biased variance of its own input batch and moves
+        `running_mean`, `running_var` and `num_batches_tracked` as nn.BatchNorm2d in training mode does.  The block stays
+        in eval mode: `training` is False, and `train(True)` keeps refusing to run."""
+        self.batch_stats = bool(mode)
+        return self
 
     def forward(self, x):
         from .grad import block_forward
@@ -64,14 +76,22 @@ class PhaseNet(PackedModule):
         self.max_amplitudes = None
         self.max_low_level = None
         self.fine_tuning = False
+        self.batch_stats = False
         self.train(False)
         self.to(self.device)
 
-    def fine_tune(self, mode=True):
-        """Fixed-statistics fine-tuning on or off (off in a new module).  It is PhaseNet's counterpart of FusionNet's
-        training mode: `train(True)` would mean batch statistics, which are not built, and a new module's parameters
-        require grad, so callers that never backpropagate keep results without a grad_fn unless they ask here."""
+    def fine_tune(self, mode=True, batch_stats=False):
+        """Training on or off (off in a new module).  It is PhaseNet's counterpart of FusionNet's training mode: a new
+        module's parameters require grad, so callers that never backpropagate keep results without a grad_fn unless they
+        ask here.  `fine_tune()` is fixed-statistics fine-tuning: BatchNorm on the running statistics of the checkpoint.
+        `fine_tune(batch_stats=True)` is the reference's training mode (src/train/train.py:90, trainer.py:107-134): it sets
+        every block's `batch_stats` flag, and every forward from then on, grad mode or not, normalises with the batch's
+        statistics and moves the running ones.  `fine_tune(False)` clears both.  The module stays in eval mode throughout
+        (`training` is False); `train(True)` keeps raising."""
         self.fine_tuning = bool(mode)
+        self.batch_stats = self.fine_tuning and bool(batch_stats)
+        for blk in self.layers:
+            blk.batch_statistics(self.batch_stats)
         return self
 
     # -- weights ------------------------------------------------------------------------------------
@@ -155,7 +175,7 @@ class PhaseNet(PackedModule):
             m = self.pyr.height - 2
         if self.max_amplitudes is None:
             raise RuntimeError("call normalize_vals(vals) before forward(vals) (phase_net.py two-call protocol)")
-        if self.fine_tuning and torch.is_grad_enabled() and any(p.requires_grad for p in self.layers.parameters()):
+        if self.fine_tuning and (self.batch_stats or (torch.is_grad_enabled() and any(p.requires_grad for p in self.layers.parameters()))):
             return self._forward_grad(vals, m)
         packed = self.packed()
         low_in = vals.low_level.contiguous()
@@ -216,7 +236,9 @@ class PhaseNet(PackedModule):
     def _forward_grad(self, vals, m):
         """The same walk as a graph of the nodes of vfi_amd/phase_net/grad.py, in the reference's
         channel order [feature | phase | amp | prediction]: fixed-statistics fine-tuning.  Taken only after fine_tune(), with grad
-        mode on and a parameter of self.layers requiring grad.  The normalised inputs and the maxima get no gradient."""
+        mode on and a parameter of self.layers requiring grad -- or, after fine_tune(batch_stats=True), by every call (section 17:
+        each block takes its batch's statistics; the shared last block takes fresh ones at every level it serves and moves its
+        running statistics once per level, coarse to fine).  The normalised inputs and the maxima get no gradient."""
         from . import grad as G
         low_in = vals.low_level.detach().contiguous()
         f, c = G.block_forward(self.layers[0], low_in)                                     # :113

@@ -474,6 +474,35 @@ int vfi_phasenet_predict_backward(const float *feat, long long feat_bstride, con
                                   long long gpi_bstride, float *grad_feat, long long gf_bstride, float *grad_weight,
                                   float *grad_bias, float *workspace, int N, int HW, vfi_stream_t stream);
 
+/* Batch-statistics BatchNorm of a block (reference src/phase_net/block.py:17, nn.BatchNorm2d in training mode, with the ELU
+ * of block.py:18): per-channel mean[c] and BIASED variance var[c] of y (N, C, HW; batch stride y_bstride) over the samples
+ * and pixels.  Two stages: every channel's N * HW values are cut into equal chunks by (N, C, HW) alone, one block writes
+ * (count, mean, M2) of each chunk, one final block per channel merges them in chunk order with Chan's formula -- never
+ * E[y^2] - E[y]^2.  `workspace`: VFI_REDUCE_WORKSPACE_FLOATS (C * chunks * 3 partials fit by the choice of the cut;
+ * C <= 1365).  N * HW < 2 is VFI_ERR_SHAPE (torch: "Expected more than 1 value per channel when training").  16-byte
+ * accesses when HW, the stride and the base allow, 4-byte otherwise. */
+int vfi_bn_stats(const float *y, long long y_bstride, int N, int C, int HW, float *mean, float *var, float *workspace,
+                 vfi_stream_t stream);
+
+/* out = act(gamma (y - mean) / sqrt(var + eps) + beta) per channel (block.py:17-18 in training mode, F.batch_norm's
+ * normalisation): act = VFI_ACT_NONE or VFI_ACT_ELU; mean, var as vfi_bn_stats wrote them (or any statistics); one read and
+ * one write, the scale formed once per block.  out may be y itself. */
+int vfi_bn_act_forward(const float *y, long long y_bstride, const float *mean, const float *var, const float *gamma,
+                       const float *beta, float eps, int act, float *out, long long out_bstride, int N, int C, int HW,
+                       vfi_stream_t stream);
+
+/* Adjoint of vfi_bn_stats + vfi_bn_act_forward (block.py:17-18, nn.BatchNorm2d in training mode: the statistics depend on
+ * y).  g_t: gradient of the output t; t: that output (read for VFI_ACT_ELU only, may be NULL otherwise); y: the kept input.
+ * With g_z = g_t act'(t) (ELU' from the output: t > 0 ? 1 : t + 1), xhat = (y - mean) / sqrt(var + eps), n = N * HW:
+ *   g_beta[c] = sum g_z,  g_gamma[c] = sum g_z xhat           (two stages over `workspace`, VFI_REDUCE_WORKSPACE_FLOATS,
+ *                                                              the cut and the order of vfi_bn_stats)
+ *   g_y = gamma / sqrt(var + eps) * (g_z - g_beta / n - xhat g_gamma / n)
+ * g_y may be g_t itself; g_y NULL skips that pass (gamma may then be NULL). */
+int vfi_bn_act_backward(const float *g_t, long long gt_bstride, const float *t, long long t_bstride, const float *y,
+                        long long y_bstride, const float *mean, const float *var, const float *gamma, float eps, int act,
+                        float *g_y, long long gy_bstride, float *g_gamma, float *g_beta, float *workspace, int N, int C,
+                        int HW, vfi_stream_t stream);
+
 /* out[0] = scale / count * sum |w(a - b)| over `count` floats, w(d) = atan2(sin d, cos d) when wrap != 0, else d.
  * wrap = 0, scale = 1: nn.L1Loss (loss.py:8,20).  wrap = 1, scale = nbands, a = the target's and b = the output's phases
  * of one level: that level's term of the phase loss, the sum over the orientations of the mean |delta_psi| (loss.py:10-16).

@@ -2,7 +2,12 @@
 """Cost of fine-tuning the whole PhaseNet on a 1080x1920 Lab frame pair (N = 3 colours): the inference
 forward of the coarse-to-fine walk, the same forward as an autograd graph, and the HIP backward of one full step, at full m
 and at m = 4; and the head adjoint at the finest level's shape, vfi_phasenet_predict_backward against the five-launch
-composition of the section-14 entry points.  Per-call HIP events."""
+composition of the section-14 entry points.  Per-call HIP events.
+
+--batch-stats: the same step with BatchNorm on the batch's statistics (the forward without a graph is
+then that route under no_grad, running statistics updated), and the three batch-statistics kernels alone at the finest level's
+shape (3 x 64 x 1080 x 1920) with their algorithmic bytes."""
+import argparse
 import math
 import os
 import sys
@@ -48,10 +53,29 @@ def head(h, w, n=3, iters=10, warm=3):
           f"five-launch composition {t_old:.3f} ms, ratio {t_old / t_new:.2f}")
 
 
-def step(h, w, m, n=3, iters=3, warm=1):
+def bn_kernels(h, w, n=3, c=64, iters=10, warm=3):
+    dev = torch.device("cuda:0")
+    g = torch.Generator().manual_seed(0)
+    y = torch.randn((n, c, h, w), device=dev) * 1.5 + 0.5
+    g_t = torch.randn((n, c, h, w), device=dev)
+    gamma, beta = (torch.rand(c, generator=g) + 0.5).to(dev), torch.randn(c, generator=g).to(dev)
+    mean, var = ops.bn_stats(y)
+    t = ops.bn_act_forward(y, mean, var, gamma, beta, 1e-5, "elu")
+    planes = 4e-9 * n * c * h * w
+    rows = [("vfi_bn_stats", 1, lambda: ops.bn_stats(y)),
+            ("vfi_bn_act_forward (elu)", 2, lambda: ops.bn_act_forward(y, mean, var, gamma, beta, 1e-5, "elu", out=t)),
+            ("vfi_bn_act_backward, reductions only", 3, lambda: ops.bn_act_backward(g_t, t, y, mean, var, gamma, 1e-5, "elu", need_data=False)),
+            ("vfi_bn_act_backward, in place", 7, lambda: ops.bn_act_backward(g_t, t, y, mean, var, gamma, 1e-5, "elu", out=g_t))]
+    print(f"batch-statistics kernels, N={n} C={c} {h}x{w} ({planes:.2f} GB per tensor)")
+    for name, passes, fn in rows:
+        ms = timed(fn, iters, warm)
+        print(f"  {name:40s} {ms:7.3f} ms  {passes * planes / (ms * 1e-3):6.0f} GB/s of {passes} tensor passes")
+
+
+def step(h, w, m, n=3, iters=3, warm=1, batch_stats=False):
     dev = torch.device("cuda:0")
     height = calc_pyr_height(torch.empty(1, h, w))
-    core = PhaseNetCore(height, dev).fine_tune()
+    core = PhaseNetCore(height, dev).fine_tune(batch_stats=batch_stats)
     core.load_state_dict(W.net_state(0))
     pyr = Pyramid(height=height, nbands=4, scale_factor=W.S2, device=dev)
     imgs = torch.rand((2 * n, h, w), generator=torch.Generator().manual_seed(1)).to(dev)
@@ -79,17 +103,24 @@ def step(h, w, m, n=3, iters=3, warm=1):
         loss().backward()
     t_step = timed(full, iters, warm)
     t_bwd = t_step - t_fwd
-    print(f"PhaseNet walk, N={n} {h}x{w}, height {height}, m = {m if m is not None else height - 2}")
-    print(f"  inference forward          {t_inf:8.3f} ms")
+    print(f"PhaseNet walk, N={n} {h}x{w}, height {height}, m = {m if m is not None else height - 2}" +
+          (", batch statistics" if batch_stats else ""))
+    print(f"  {'forward without a graph' if batch_stats else 'inference forward'      :26s} {t_inf:8.3f} ms")
     print(f"  forward as a graph + loss  {t_fwd:8.3f} ms")
-    print(f"  backward                   {t_bwd:8.3f} ms = {t_bwd / t_inf:.2f} x inference forward")
+    print(f"  backward                   {t_bwd:8.3f} ms = {t_bwd / t_inf:.2f} x that forward")
 
 
 def main():
-    head(1080, 1920)
+    ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
+    ap.add_argument("--batch-stats", action="store_true", help="BatchNorm on batch statistics (DESIGN.md section 17)")
+    args = ap.parse_args()
+    if args.batch_stats:
+        bn_kernels(1080, 1920)
+    else:
+        head(1080, 1920)
     torch.cuda.empty_cache()
     for m in (None, 4):
-        step(1080, 1920, m)
+        step(1080, 1920, m, batch_stats=args.batch_stats)
         torch.cuda.empty_cache()
 
 
