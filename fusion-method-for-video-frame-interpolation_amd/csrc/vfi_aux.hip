@@ -335,6 +335,40 @@ __global__ void phasenet_emit_low_kernel(const float *__restrict__ pred, long lo
     }
 }
 
+// The fusion variant with three input images (phase_net.py:158-162, 119-121): after the blend above a second one folds the
+// third image in, fb = (pred[:,8:12]+1)/2 ; amp = fb*amp + (1-fb)*amp_in[:,8:12].  pred (N,12,h,w), amp_in (N,12,h,w).  Two
+// and four images (phase_net.py:30-35,155-156: the blend reads the first two only) run phasenet_emit_kernel itself.
+__global__ void phasenet_emit_fuse_kernel(const float *__restrict__ pred, long long pred_bs, const float *__restrict__ amp_in,
+                                          long long amp_bs, const float *__restrict__ maxv, float *__restrict__ phase_out,
+                                          float *__restrict__ amp_out, int N, int HW) {
+    const long long total = (long long)N * 4 * HW;
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
+        const int p = i % HW, b = (i / HW) % 4, n = i / ((long long)HW * 4);
+        const float *pr = pred + (size_t)n * pred_bs + p;
+        const float *am = amp_in + (size_t)n * amp_bs + p;
+        const float beta = (pr[(size_t)(4 + b) * HW] + 1.0f) / 2.0f;
+        const float a = fmaf(beta, am[(size_t)(4 + b) * HW], (1.0f - beta) * am[(size_t)b * HW]);
+        const float fb = (pr[(size_t)(8 + b) * HW] + 1.0f) / 2.0f;
+        const float a3 = fmaf(fb, a, (1.0f - fb) * am[(size_t)(8 + b) * HW]);      // (spelled out: vfi_phasenet_predict_n computes the same bits)
+        phase_out[i] = pr[(size_t)b * HW] * 3.14159265358979323846f;
+        amp_out[i] = a3 * maxv[n];
+    }
+}
+// ... and the low level's (phase_net.py:119-121): fa = (pred[:,1]+1)/2 ; low = fa*low + (1-fa)*low[:,2], pred (N,2,h,w)
+__global__ void phasenet_emit_low_fuse_kernel(const float *__restrict__ pred, long long pred_bs, const float *__restrict__ low,
+                                              long long low_bs, const float *__restrict__ maxv, float *__restrict__ out,
+                                              int N, int HW) {
+    const long long total = (long long)N * HW;
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
+        const int p = i % HW, n = i / HW;
+        const float *pr = pred + (size_t)n * pred_bs + p;
+        const float alpha = (pr[0] + 1.0f) / 2.0f, fa = (pr[HW] + 1.0f) / 2.0f;
+        const float *l = low + (size_t)n * low_bs + p;
+        const float two = alpha * l[0] + (1.0f - alpha) * l[HW];
+        out[i] = (fa * two + (1.0f - fa) * l[(size_t)2 * HW]) * maxv[n];
+    }
+}
+
 // ---- FusionNet tail: clamp(base + tanh(x), 0, 1)  (fusion_net.py:70-77) ----------------------------------------
 __global__ void tanh_residual_clamp_kernel(const float *__restrict__ x, const float *__restrict__ base,
                                            float *__restrict__ y, long long total) {
@@ -447,6 +481,35 @@ extern "C" int vfi_phasenet_emit_low(const float *pred, long long pred_bstride, 
     LAUNCH_1D(phasenet_emit_low_kernel, (long long)N * HW, stream, pred, pred_bstride, low_in, low_bstride, max_low,
               low_out, N, HW);
     return vfi::check_launch("vfi_phasenet_emit_low");
+}
+
+extern "C" int vfi_phasenet_emit_n(const float *pred, long long pred_bstride, const float *amp_in, long long amp_bstride,
+                                   const float *max_amp, float *phase_out, float *amp_out, int N, int HW, int num_img,
+                                   vfi_stream_t stream) {
+    VFI_REQUIRE(pred && amp_in && max_amp && phase_out && amp_out, VFI_ERR_INVALID_ARG, "vfi_phasenet_emit_n: null pointer");
+    VFI_REQUIRE(N > 0 && HW > 0, VFI_ERR_INVALID_ARG, "vfi_phasenet_emit_n: bad sizes");
+    VFI_REQUIRE(num_img >= 2 && num_img <= 4, VFI_ERR_UNSUPPORTED, "vfi_phasenet_emit_n: num_img %d (2, 3 or 4)", num_img);
+    if (num_img == 3)
+        LAUNCH_1D(phasenet_emit_fuse_kernel, (long long)N * 4 * HW, stream, pred, pred_bstride, amp_in, amp_bstride, max_amp,
+                  phase_out, amp_out, N, HW);
+    else        // the blend of two images, whatever follows them in amp_in
+        LAUNCH_1D(phasenet_emit_kernel, (long long)N * 4 * HW, stream, pred, pred_bstride, amp_in, amp_bstride, max_amp,
+                  phase_out, amp_out, N, HW);
+    return vfi::check_launch("vfi_phasenet_emit_n");
+}
+
+extern "C" int vfi_phasenet_emit_low_n(const float *pred, long long pred_bstride, const float *low_in, long long low_bstride,
+                                       const float *max_low, float *low_out, int N, int HW, int num_img, vfi_stream_t stream) {
+    VFI_REQUIRE(pred && low_in && max_low && low_out, VFI_ERR_INVALID_ARG, "vfi_phasenet_emit_low_n: null pointer");
+    VFI_REQUIRE(N > 0 && HW > 0, VFI_ERR_INVALID_ARG, "vfi_phasenet_emit_low_n: bad sizes");
+    VFI_REQUIRE(num_img >= 2 && num_img <= 4, VFI_ERR_UNSUPPORTED, "vfi_phasenet_emit_low_n: num_img %d (2, 3 or 4)", num_img);
+    if (num_img == 3)
+        LAUNCH_1D(phasenet_emit_low_fuse_kernel, (long long)N * HW, stream, pred, pred_bstride, low_in, low_bstride, max_low,
+                  low_out, N, HW);
+    else
+        LAUNCH_1D(phasenet_emit_low_kernel, (long long)N * HW, stream, pred, pred_bstride, low_in, low_bstride, max_low,
+                  low_out, N, HW);
+    return vfi::check_launch("vfi_phasenet_emit_low_n");
 }
 
 extern "C" int vfi_tanh_residual_clamp(const float *x, const float *base, float *y, long long count,

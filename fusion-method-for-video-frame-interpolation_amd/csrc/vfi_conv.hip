@@ -549,6 +549,85 @@ __global__ __launch_bounds__(256) void phasenet_predict_kernel(const float *__re
     }
 }
 
+// ---- ... for the fusion variant with three input images (phase_net.py:23-29, 158-162): the map is 64 -> 12, and a second blend
+// folds the third image's amplitudes in, fb = (pred[8:12] + 1) / 2 ; amp = fb * amp + (1 - fb) * amp_in[8:12] -- to the bit what
+// conv1x1_stream_kernel<3, 16, VEC> (its 12 live outputs, the same FMA chain over the channels) followed by vfi_phasenet_emit_n
+// gives.  48 accumulators and 32 loaded floats per thread at VEC = 4.  A sibling of phasenet_predict_kernel, not a template
+// parameter of it: the two-image kernel's code stays as it is.
+template <int VEC>
+__global__ __launch_bounds__(256) void phasenet_predict_fuse_kernel(const float *__restrict__ x, long long x_bs, const float *__restrict__ wp,
+                                                                    const float *__restrict__ bias, int Cout_pad, const float *__restrict__ amp_in,
+                                                                    long long amp_bs, const float *__restrict__ maxv, float *__restrict__ pred,
+                                                                    long long pred_bs, float *__restrict__ phase_out, float *__restrict__ amp_out,
+                                                                    int Cin, int HW) {
+    typedef float vec __attribute__((ext_vector_type(VEC)));
+    constexpr int NOUT = 12;
+    const int q = blockIdx.x * 256 + threadIdx.x;
+    if (q * VEC >= HW) return;
+    const int n = blockIdx.y;
+    const vec *xp = reinterpret_cast<const vec *>(x + (size_t)n * x_bs) + q;
+    const size_t plane = (size_t)HW / VEC;
+    float acc[NOUT][VEC];
+#pragma unroll
+    for (int o = 0; o < NOUT; ++o)
+#pragma unroll
+        for (int k = 0; k < VEC; ++k) acc[o][k] = 0.0f;
+    int c = 0;
+    for (; c + 8 <= Cin; c += 8) {
+        vec v[8];
+#pragma unroll
+        for (int i = 0; i < 8; ++i) v[i] = xp[(size_t)(c + i) * plane];
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            const float *w = wp + (size_t)(c + i) * Cout_pad;
+#pragma unroll
+            for (int o = 0; o < NOUT; ++o) {
+                const float wo = w[o];
+#pragma unroll
+                for (int k = 0; k < VEC; ++k) acc[o][k] = fmaf(wo, v[i][k], acc[o][k]);
+            }
+        }
+    }
+    for (; c < Cin; ++c) {
+        const vec v = xp[(size_t)c * plane];
+        const float *w = wp + (size_t)c * Cout_pad;
+#pragma unroll
+        for (int o = 0; o < NOUT; ++o) {
+            const float wo = w[o];
+#pragma unroll
+            for (int k = 0; k < VEC; ++k) acc[o][k] = fmaf(wo, v[k], acc[o][k]);
+        }
+    }
+    vec *pp = reinterpret_cast<vec *>(pred + (size_t)n * pred_bs) + q;
+#pragma unroll
+    for (int o = 0; o < NOUT; ++o) {
+        const float b = bias ? bias[o] : 0.0f;
+        vec r;
+#pragma unroll
+        for (int k = 0; k < VEC; ++k) r[k] = acc[o][k] = apply_act(acc[o][k] + b, 3);
+        pp[(size_t)o * plane] = r;
+    }
+    const vec *ap = reinterpret_cast<const vec *>(amp_in + (size_t)n * amp_bs) + q;
+    vec *pho = reinterpret_cast<vec *>(phase_out + (size_t)n * 4 * HW) + q, *amo = reinterpret_cast<vec *>(amp_out + (size_t)n * 4 * HW) + q;
+    const float mx = maxv[n];
+#pragma unroll
+    for (int b = 0; b < 4; ++b) {
+        const vec a0 = ap[(size_t)b * plane], a1 = ap[(size_t)(4 + b) * plane], a2 = ap[(size_t)(8 + b) * plane];
+        vec ph, am;
+#pragma unroll
+        for (int k = 0; k < VEC; ++k) {
+            const float beta = (acc[4 + b][k] + 1.0f) / 2.0f;
+            const float a = fmaf(beta, a1[k], (1.0f - beta) * a0[k]);
+            const float fb = (acc[8 + b][k] + 1.0f) / 2.0f;
+            const float a3 = fmaf(fb, a, (1.0f - fb) * a2[k]);
+            ph[k] = acc[b][k] * 3.14159265358979323846f;
+            am[k] = a3 * mx;
+        }
+        pho[(size_t)b * plane] = ph;
+        amo[(size_t)b * plane] = am;
+    }
+}
+
 void vfi::conv::launch_splitk_reduce(const ConvArgs &b, int N, hipStream_t s) {
     const int HW = b.H * b.W;
     const bool vec = HW % 4 == 0 && (reinterpret_cast<uintptr_t>(b.y) & 15u) == 0 && b.y_bs % 4 == 0 &&
@@ -723,6 +802,38 @@ extern "C" int vfi_phasenet_predict(const float *feat, long long feat_bstride, c
         hipLaunchKernelGGL(phasenet_predict_kernel<2>, grid, dim3(256), 0, s, feat, feat_bstride, packed_w, bias, 32, amp_in, amp_bstride, max_amp, pred,
                            pred_bstride, phase_out, amp_out, Cin, (int)HW);
     return vfi::check_launch("vfi_phasenet_predict");
+}
+
+extern "C" int vfi_phasenet_predict_n(const float *feat, long long feat_bstride, const float *packed_w, const float *bias,
+                                      const float *amp_in, long long amp_bstride, const float *max_amp, float *pred, long long pred_bstride,
+                                      float *phase_out, float *amp_out, int N, int Cin, int H, int W, int num_img, vfi_stream_t stream) {
+    VFI_REQUIRE(feat && packed_w && amp_in && max_amp && pred && phase_out && amp_out, VFI_ERR_INVALID_ARG, "vfi_phasenet_predict_n: null pointer");
+    VFI_REQUIRE(N > 0 && N <= 65535 && Cin > 0 && H > 0 && W > 0, VFI_ERR_INVALID_ARG, "vfi_phasenet_predict_n: bad sizes");
+    VFI_REQUIRE(num_img >= 2 && num_img <= 4, VFI_ERR_UNSUPPORTED, "vfi_phasenet_predict_n: num_img %d (2, 3 or 4)", num_img);
+    if (num_img != 3)       // 64 -> 8 and the blend of the first two images (phase_net.py:30-35,155-156): the two-image head itself
+        return vfi_phasenet_predict(feat, feat_bstride, packed_w, bias, amp_in, amp_bstride, max_amp, pred, pred_bstride, phase_out, amp_out, N,
+                                    Cin, H, W, stream);
+    const long long HW = (long long)H * W;
+    VFI_REQUIRE((long long)Cin * HW < (1ll << 31), VFI_ERR_UNSUPPORTED, "vfi_phasenet_predict_n: per-sample tensor too large for 32-bit offsets");
+    ConvArgs a{};
+    a.x = feat; a.y = pred; a.x_bs = feat_bstride; a.y_bs = pred_bstride; a.Cout = 12; a.H = H; a.W = W;
+    int vec = conv1x1_stream_vec(a, 1);
+    const uintptr_t bits = reinterpret_cast<uintptr_t>(amp_in) | reinterpret_cast<uintptr_t>(phase_out) | reinterpret_cast<uintptr_t>(amp_out) | (uintptr_t)(amp_bstride * 4);
+    if (vec == 4 && (bits & 15u)) vec = (bits & 7u) ? 0 : 2;
+    else if (vec == 2 && (bits & 7u)) vec = 0;
+    if (!vec) {        // small or odd levels: the two launches this entry point replaces
+        const int rc = conv2d_impl(feat, feat_bstride, packed_w, bias, nullptr, 0, pred, pred_bstride, N, Cin, H, W, 12, 1, 0, 3, false, nullptr, 0, stream);
+        return rc ? rc : vfi_phasenet_emit_n(pred, pred_bstride, amp_in, amp_bstride, max_amp, phase_out, amp_out, N, (int)HW, 3, stream);
+    }
+    const dim3 grid((unsigned)vfi::ceil_div((int)(HW / vec), 256), (unsigned)N);
+    hipStream_t s = vfi::as_stream(stream);
+    if (vec == 4)
+        hipLaunchKernelGGL(phasenet_predict_fuse_kernel<4>, grid, dim3(256), 0, s, feat, feat_bstride, packed_w, bias, 32, amp_in, amp_bstride, max_amp, pred,
+                           pred_bstride, phase_out, amp_out, Cin, (int)HW);
+    else
+        hipLaunchKernelGGL(phasenet_predict_fuse_kernel<2>, grid, dim3(256), 0, s, feat, feat_bstride, packed_w, bias, 32, amp_in, amp_bstride, max_amp, pred,
+                           pred_bstride, phase_out, amp_out, Cin, (int)HW);
+    return vfi::check_launch("vfi_phasenet_predict_n");
 }
 
 extern "C" int vfi_conv2d_pool2(const float *x, long long x_bstride, const float *packed_w, const float *bias, float *y,

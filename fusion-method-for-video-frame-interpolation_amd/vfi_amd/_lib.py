@@ -43,6 +43,9 @@ SIGNATURES = {
     "vfi_phasenet_emit": [c_f, c_l, c_f, c_l, c_f, c_f, c_f, c_i, c_i, c_s],
     "vfi_phasenet_predict": [c_f, c_l, c_f, c_f, c_f, c_l, c_f, c_f, c_l, c_f, c_f, c_i, c_i, c_i, c_i, c_s],
     "vfi_phasenet_emit_low": [c_f, c_l, c_f, c_l, c_f, c_f, c_i, c_i, c_s],
+    "vfi_phasenet_emit_n": [c_f, c_l, c_f, c_l, c_f, c_f, c_f, c_i, c_i, c_i, c_s],
+    "vfi_phasenet_predict_n": [c_f, c_l, c_f, c_f, c_f, c_l, c_f, c_f, c_l, c_f, c_f, c_i, c_i, c_i, c_i, c_i, c_s],
+    "vfi_phasenet_emit_low_n": [c_f, c_l, c_f, c_l, c_f, c_f, c_i, c_i, c_i, c_s],
     "vfi_tanh_residual_clamp": [c_f, c_f, c_f, c_l, c_s],
     "vfi_rgb2lab": [c_f, c_f, c_i, c_i, c_s],
     "vfi_lab2rgb": [c_f, c_f, c_i, c_i, c_s],

@@ -717,6 +717,67 @@ def phasenet_emit_low(pred, low_in, max_low):
     return low
 
 
+# ---- PhaseNet's level head with two, three or four input images ------------------------------------
+def phasenet_pred_channels(num_img):
+    """(low level's, a band level's) prediction channels of PhaseNet(num_img) (reference phase_net.py:23-35)."""
+    if num_img not in (2, 3, 4):
+        raise VfiLibraryError(f"PhaseNet has 2, 3 or 4 input images, not {num_img}")
+    return (2, 12) if num_img == 3 else (1, 8)
+
+
+def phasenet_emit_n(pred, amp_in, max_amp, num_img):
+    """phasenet_emit for num_img images (vfi_phasenet_emit_n): pred (N,P,H,W), P = 12 for three images and 8 otherwise, amp_in
+    (N,4*num_img,H,W), max_amp (N,) -> (phase, amp), each (N*4,1,H,W).  Three images: the second blend with amp_in[:,8:12]."""
+    p_band = phasenet_pred_channels(num_img)[1]
+    n, c, h, w = pred.shape
+    if c != p_band or tuple(amp_in.shape) != (n, 4 * num_img, h, w) or max_amp.numel() != n:
+        raise VfiLibraryError(f"phasenet_emit_n: pred must be (N,{p_band},H,W), amp_in (N,{4 * num_img},H,W), max_amp (N,)")
+    pp, ps = _slice_ptr(pred, "pred")
+    ap, as_ = _slice_ptr(amp_in, "amp_in")
+    phase, amp = new((n * 4, 1, h, w), pred), new((n * 4, 1, h, w), pred)
+    _lib.call("vfi_phasenet_emit_n", pp, ps, ap, as_, _lib.dptr(max_amp, "max_amp"), phase.data_ptr(), amp.data_ptr(), n, h * w,
+              num_img, _lib.stream_ptr())
+    return phase, amp
+
+
+def phasenet_emit_low_n(pred, low_in, max_low, num_img):
+    """phasenet_emit_low for num_img images (vfi_phasenet_emit_low_n): pred (N,P,H,W), P = 2 for three images and 1 otherwise,
+    low_in (N,num_img,H,W) normalised, max_low (N,) -> (N,1,H,W)."""
+    p_low = phasenet_pred_channels(num_img)[0]
+    n, c, h, w = pred.shape
+    if c != p_low or tuple(low_in.shape) != (n, num_img, h, w) or max_low.numel() != n:
+        raise VfiLibraryError(f"phasenet_emit_low_n: pred must be (N,{p_low},H,W), low_in (N,{num_img},H,W), max_low (N,)")
+    pp, ps = _slice_ptr(pred, "pred")
+    lp, ls = _slice_ptr(low_in, "low_in")
+    low = new((n, 1, h, w), pred)
+    _lib.call("vfi_phasenet_emit_low_n", pp, ps, lp, ls, _lib.dptr(max_low, "max_low"), low.data_ptr(), n, h * w, num_img,
+              _lib.stream_ptr())
+    return low
+
+
+def phasenet_predict_n(feat, pc, amp_in, max_amp, num_img, pred=None):
+    """phasenet_predict for num_img images (vfi_phasenet_predict_n): feat (N,64,H,W), pc the PackedConv of the 64 -> P 1x1
+    prediction map (P = 12 for three images, 8 otherwise), amp_in (N,4*num_img,H,W), max_amp (N,) -> (pred (N,P,H,W) post-tanh,
+    phase, amp (N*4,1,H,W)).  Small or odd-sized levels run vfi_conv2d + vfi_phasenet_emit_n inside the library."""
+    p_band = phasenet_pred_channels(num_img)[1]
+    n, cin, h, w = feat.shape
+    if pc.cout != p_band or pc.ks != 1 or pc.cin != cin or tuple(amp_in.shape) != (n, 4 * num_img, h, w) or max_amp.numel() != n:
+        raise VfiLibraryError(f"phasenet_predict_n: needs a 1x1 map with {p_band} outputs, amp_in (N,{4 * num_img},H,W) and max_amp (N,)")
+    if pred is None:
+        pred = new((n, p_band, h, w), feat)
+    elif tuple(pred.shape) != (n, p_band, h, w):
+        raise VfiLibraryError(f"phasenet_predict_n: pred shape {tuple(pred.shape)} != {(n, p_band, h, w)}")
+    fp, fs = _slice_ptr(feat, "feat")
+    ap, as_ = _slice_ptr(amp_in, "amp_in")
+    pp, ps = _slice_ptr(pred, "pred")
+    phase, amp = new((n * 4, 1, h, w), feat), new((n * 4, 1, h, w), feat)
+    planes = cin + p_band + 8 + (12 if num_img == 3 else 8)             # read: features, the blended amplitudes; written: pred, outputs
+    _lib.call("vfi_phasenet_predict_n", fp, fs, pc.packed.data_ptr(), pc.bias.data_ptr(), ap, as_, _lib.dptr(max_amp, "max_amp"),
+              pp, ps, phase.data_ptr(), amp.data_ptr(), n, cin, h, w, num_img, _lib.stream_ptr(),
+              work=_prof("byte", 4.0 * n * planes * h * w, "phasenet_predict_fuse_kernel" if num_img == 3 else "phasenet_predict_kernel"))
+    return pred, phase, amp
+
+
 def phasenet_emit_low_backward(grad_low, low_in, max_low):
     n, _, h, w = low_in.shape
     if grad_low.numel() != n * h * w:

@@ -52,7 +52,8 @@ class PhaseNet(torch.nn.Module):
     def _forward(self, img_batch, high_level, ada_pred, m):
         img_batch = img_batch.float()
         if m is None:                                                    # fused route (architecture.py:40-59)
-            vals, bufs = self.pyr.filter(img_batch, concat_frames=self.core.num_img, phase_scale=1.0 / math.pi)
+            vals, bufs = self.pyr.filter(img_batch, concat_frames=self.core.num_img, phase_scale=1.0 / math.pi,
+                                         pred_channels=self.core.pred_channels)
             vals_pred = self.core(self.core.normalize_vals(vals, concat=bufs), None)
             vals_target = None
         else:                                                            # hierarchical form with a target image

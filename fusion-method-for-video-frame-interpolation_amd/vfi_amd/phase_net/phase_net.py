@@ -1,5 +1,5 @@
-"""PhaseNet -- mirror of reference src/phase_net/phase_net.py (the variant the fused path uses:
-`PhaseNet(pyr, device, num_img=2)`, two-call protocol `normalize_vals(vals)` then `forward(vals)`).
+"""PhaseNet -- mirror of reference src/phase_net/phase_net.py (`PhaseNet(pyr, device, num_img)`; the fused path uses
+num_img=2; two-call protocol `normalize_vals(vals)` then `forward(vals)`).
 
 Execution on the MI355X (all arithmetic in libvfi_hip.so):
   * block = [conv k, BN(eval), ELU, conv k, ELU] -> 64 features; [1x1 conv, tanh] -> prediction
@@ -12,6 +12,10 @@ Execution on the MI355X (all arithmetic in libvfi_hip.so):
     channels, and normalize_vals writes phase/pi and amp/max straight into the last 16;
   * the per-level blend + de-normalisation (phase_net.py:155-168, :80-105) is one launch per level.
 Maxima are returned/kept per call on the module (as the reference does, phase_net.py:53,59,70).
+
+`num_img` = 3 and 4 are the reference's pyramid-domain fusion networks (phase_net.py:21-35, 119-121, 158-162; DESIGN.md section
+18): the buffers are [feature 64 | prediction P | phase 4*num_img | amp 4*num_img] with P = `pred_channels`, the heads are
+vfi_phasenet_predict_n / vfi_phasenet_emit_low_n.  Inference only.
 
 After `fine_tune()`, with grad mode on and a parameter of `layers` requiring grad, `forward` takes a second route,
 `_forward_grad`: the same walk as an autograd graph with HIP backward kernels, BatchNorm on its running statistics (DESIGN.md
@@ -62,16 +66,18 @@ class PhaseNetBlock(torch.nn.Module):
 class PhaseNet(PackedModule):
     def __init__(self, pyr, device, num_img=2):
         super().__init__()
-        if num_img != 2:
-            raise NotImplementedError("vfi_amd.PhaseNet implements the two-frame network of the fused path")
+        if num_img not in (2, 3, 4):
+            raise NotImplementedError("vfi_amd.PhaseNet implements the reference's networks of two, three and four input images")
         self.pyr = pyr
         self.device = torch.device(device)
         self.num_img = num_img
         self.eps = 1e-8
-        blocks = [PhaseNetBlock(num_img, 64, 1, (1, 1)),
-                  PhaseNetBlock(64 + 1 + 8 * num_img, 64, 8, (1, 1)),
-                  PhaseNetBlock(64 + 8 + 8 * num_img, 64, 8, (1, 1))]
-        blocks += [PhaseNetBlock(64 + 8 + 8 * num_img, 64, 8, (3, 3)) for _ in range(5)]
+        # phase_net.py:23-35: three images predict one more low-level weight and four more amplitude weights per level
+        p_low, p_band = self.pred_channels
+        blocks = [PhaseNetBlock(num_img, 64, p_low, (1, 1)),
+                  PhaseNetBlock(64 + p_low + 8 * num_img, 64, p_band, (1, 1)),
+                  PhaseNetBlock(64 + p_band + 8 * num_img, 64, p_band, (1, 1))]
+        blocks += [PhaseNetBlock(64 + p_band + 8 * num_img, 64, p_band, (3, 3)) for _ in range(5)]
         self.layers = torch.nn.ModuleList(blocks)
         self.max_amplitudes = None
         self.max_low_level = None
@@ -80,6 +86,12 @@ class PhaseNet(PackedModule):
         self.train(False)
         self.to(self.device)
 
+    @property
+    def pred_channels(self):
+        """(low level's, a band level's) prediction channels: (2, 12) for three input images, else (1, 8) (phase_net.py:23-35);
+        what Pyramid.filter(concat_frames=num_img, pred_channels=...) lays the block-input buffers out for."""
+        return ops.phasenet_pred_channels(self.num_img)
+
     def fine_tune(self, mode=True, batch_stats=False):
         """Training on or off (off in a new module).  It is PhaseNet's counterpart of FusionNet's training mode: a new
         module's parameters require grad, so callers that never backpropagate keep results without a grad_fn unless they
@@ -87,7 +99,9 @@ class PhaseNet(PackedModule):
         `fine_tune(batch_stats=True)` is the reference's training mode (src/train/train.py:90, trainer.py:107-134): it sets
         every block's `batch_stats` flag, and every forward from then on, grad mode or not, normalises with the batch's
         statistics and moves the running ones.  `fine_tune(False)` clears both.  The module stays in eval mode throughout
-        (`training` is False); `train(True)` keeps raising."""
+        (`training` is False); `train(True)` keeps raising.  The networks of three and four input images run inference only."""
+        if mode and self.num_img != 2:
+            raise NotImplementedError("training of the fusion variants (num_img = 3, 4) is not built: PhaseNet.fine_tune needs num_img = 2")
         self.fine_tuning = bool(mode)
         self.batch_stats = self.fine_tuning and bool(batch_stats)
         for blk in self.layers:
@@ -100,10 +114,11 @@ class PhaseNet(PackedModule):
         for i, blk in enumerate(self.layers):
             w = blk.feature_map[0].weight
             if i >= 1:
-                # reference channel order [feature 64 | phase 8 | amp 8 | pred P] -> ours
-                # [feature 64 | pred P | phase 8 | amp 8]
-                p = w.shape[1] - 80
-                perm = list(range(64)) + list(range(80, 80 + p)) + list(range(64, 80))
+                # reference channel order [feature 64 | phase 4F | amp 4F | pred P] -> ours
+                # [feature 64 | pred P | phase 4F | amp 4F], F = num_img
+                pa = 64 + 8 * self.num_img
+                p = w.shape[1] - pa
+                perm = list(range(64)) + list(range(pa, pa + p)) + list(range(64, pa))
                 w = w[:, perm]
             c1 = ops.PackedConv(w, blk.feature_map[0].bias, bn=blk.feature_map[1].fold_args())
             out.append((c1, self.pack(blk.feature_map[3]), self.pack(blk.prediction_map[0])))
@@ -111,7 +126,7 @@ class PhaseNet(PackedModule):
 
     # -- normalisation (phase_net.py:42-78) -------------------------------------------------------------
     def normalize_vals(self, vals, concat=None, amp_max=None):
-        """phase_net.py:42-78.  `concat` (from Pyramid.filter(concat_frames=2, phase_scale=1/pi)): the block-input
+        """phase_net.py:42-78.  `concat` (from Pyramid.filter(concat_frames=num_img, phase_scale=1/pi, pred_channels=self.pred_channels)): the block-input
         buffers that already hold phase/pi and the raw amplitudes -- then only the maxima are computed and
         the amplitudes / low level are normalised in place (no copies)."""
         if concat is not None:
@@ -123,7 +138,7 @@ class PhaseNet(PackedModule):
             amp, ph = vals.amplitude[idx].contiguous(), vals.phase[idx].contiguous()
             mx = ops.batch_max(amp, self.eps)                                   # :55
             maxes.append(mx)
-            p_prev = 1 if idx == 0 else 8
+            p_prev = self.pred_channels[0 if idx == 0 else 1]
             _, c, h, w = amp.shape
             buf = ops.new((b, 64 + p_prev + 2 * c, h, w), amp)
             pv = buf[:, 64 + p_prev:64 + p_prev + c]
@@ -194,10 +209,18 @@ class PhaseNet(PackedModule):
                 ops.conv2d(fp[:, :64], cp, "zeros", "tanh", out=fp[:, 64:])
             return fp
 
-        fp = block(0, low_in, ops.new((b, 65, hl, wl), low_in))                       # :113
+        n_img = self.num_img
+        p_low, p_band = self.pred_channels
+        fp = block(0, low_in, ops.new((b, 64 + p_low, hl, wl), low_in))               # :113
         low = ops.new((b, 1, hl, wl), low_in)
-        _lib.call("vfi_phasenet_emit_low", fp[:, 64:].data_ptr(), fp.stride(0), low_in.data_ptr(), low_in.stride(0),
-                  self.max_low_level.data_ptr(), low.data_ptr(), b, hl * wl, stream)     # :115-116 + :96-98
+        if n_img == 2:
+            _lib.call("vfi_phasenet_emit_low", fp[:, 64:].data_ptr(), fp.stride(0), low_in.data_ptr(), low_in.stride(0),
+                      self.max_low_level.data_ptr(), low.data_ptr(), b, hl * wl, stream)     # :115-116 + :96-98
+        else:                                                                          # ... + :119-121 for three images
+            if low_in.shape[1] != n_img:
+                raise RuntimeError(f"PhaseNet(num_img={n_img}): the low level has {low_in.shape[1]} images")
+            _lib.call("vfi_phasenet_emit_low_n", fp[:, 64:].data_ptr(), fp.stride(0), low_in.data_ptr(), low_in.stride(0),
+                      self.max_low_level.data_ptr(), low.data_ptr(), b, hl * wl, n_img, stream)
         hs = vals.high_level.shape
         high = torch.zeros((hs[0], 1, hs[2], hs[3]), dtype=torch.float32, device=low_in.device)   # :127-128
 
@@ -217,17 +240,22 @@ class PhaseNet(PackedModule):
             fused = packed[i][0].ks == 3 and (64 + p_prev) % 8 == 0
             if not fused:
                 ops.resize_bilinear(fp, (h, w), align_corners=False, out=x[:, :64 + p_prev])   # :138-141
-            fp = block(i, x, ops.new((b, 72, h, w), low_in), prev=fp if fused else None, head=False)
+            fp = block(i, x, ops.new((b, 64 + p_band, h, w), low_in), prev=fp if fused else None, head=False)
             amp_in = x[:, 64 + p_prev + c:]
-            p_out, a_out = ops.new((b * 4, 1, h, w), low_in), ops.new((b * 4, 1, h, w), low_in)
             # prediction map (1x1, tanh) + this level's outputs in one pass over the 64 feature channels (:149-168)
             cp = packed[i][2]
-            if cp.cout != 8 or cp.ks != 1:
-                raise RuntimeError("PhaseNet: a band level's prediction map must be a 1x1 layer with 8 outputs (phase_net.py:30-35)")
-            _lib.call("vfi_phasenet_predict", fp.data_ptr(), fp.stride(0), cp.packed.data_ptr(), cp.bias.data_ptr(), amp_in.data_ptr(),
-                      x.stride(0), self.max_amplitudes[idx].data_ptr(), fp[:, 64:].data_ptr(), fp.stride(0), p_out.data_ptr(),
-                      a_out.data_ptr(), b, 64, h, w, stream,
-                      work=("byte", 4.0 * b * (64 + 8 + 8 + 8) * h * w, "phasenet_predict_kernel") if _lib.PROFILE is not None else None)
+            if cp.cout != p_band or cp.ks != 1:
+                raise RuntimeError(f"PhaseNet: a band level's prediction map must be a 1x1 layer with {p_band} outputs (phase_net.py:23-35)")
+            if n_img == 2:
+                p_out, a_out = ops.new((b * 4, 1, h, w), low_in), ops.new((b * 4, 1, h, w), low_in)
+                _lib.call("vfi_phasenet_predict", fp.data_ptr(), fp.stride(0), cp.packed.data_ptr(), cp.bias.data_ptr(), amp_in.data_ptr(),
+                          x.stride(0), self.max_amplitudes[idx].data_ptr(), fp[:, 64:].data_ptr(), fp.stride(0), p_out.data_ptr(),
+                          a_out.data_ptr(), b, 64, h, w, stream,
+                          work=("byte", 4.0 * b * (64 + 8 + 8 + 8) * h * w, "phasenet_predict_kernel") if _lib.PROFILE is not None else None)
+            else:                # the fusion variants (section 18): 4 * num_img amplitude planes, 12 predictions for three images
+                if c != 4 * n_img:
+                    raise RuntimeError(f"PhaseNet(num_img={n_img}): level {idx} has {c} phase planes, expected {4 * n_img}")
+                _, p_out, a_out = ops.phasenet_predict_n(fp[:, :64], cp, amp_in, self.max_amplitudes[idx], n_img, pred=fp[:, 64:])
             phases.append(p_out); amps.append(a_out)
         for _ in range(self.pyr.height - 2 - m):                                           # :91-93
             phases.append(0); amps.append(0)

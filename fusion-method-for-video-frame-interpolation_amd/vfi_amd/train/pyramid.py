@@ -52,13 +52,16 @@ class Pyramid:
         self.pyr = SCFpyr_PyTorch(height=height, nbands=nbands, scale_factor=scale_factor, device=self.device)
 
     # -- analysis -------------------------------------------------------------------------------------
-    def filter(self, img, concat_frames=None, phase_scale=1.0, level_mask=None, want_high=True, want_low=True, amp_max_eps=None):
+    def filter(self, img, concat_frames=None, phase_scale=1.0, level_mask=None, want_high=True, want_low=True, amp_max_eps=None,
+               pred_channels=None):
         """Psi filter.  img (N,H,W) -> DecompValues in the per-image layout: high (N,1,H,W),
         phase/amplitude[k] (N*nbands,1,h_k,w_k) finest first with index img*nbands+band, low (N,1,hL,wL).
 
         concat_frames=F (N = F*C images ordered frame-major): PhaseNet layout instead -- phase/amplitude[k]
         are (C, F*nbands, h, w) views (channels [f0 b0..b3, f1 b0..b3]) of block-input buffers, lists ordered
-        COARSEST first, high (C,F,H,W), low (C,F,hL,wL); see PhaseNet.normalize_vals.
+        COARSEST first, high (C,F,H,W), low (C,F,hL,wL); see PhaseNet.normalize_vals.  The buffers are [feature 64 | prediction
+        P | phase F*nbands | amp F*nbands]; pred_channels=(P of the coarsest level, P of the others), default (1, 8), is
+        PhaseNet(num_img=F).pred_channels.  N = F*C is at most 16 images (the plan's limit).
 
         The per-image layout is differentiable with respect to img (autograd node `Analysis`; the gradient of the phase is
         dropped where the amplitude is exactly 0, where torch.atan2 would give NaN).  The concat_frames layout is not:
@@ -68,6 +71,9 @@ class Pyramid:
             raise VfiLibraryError("Pyramid.filter expects (N,H,W)")
         img = img.contiguous()
         n, h, w = img.shape
+        if concat_frames is not None and n > 16:
+            raise VfiLibraryError(f"Pyramid.filter(concat_frames={int(concat_frames)}): {n} images (frames x colours), a plan "
+                                  "holds at most 16")
         plan = self.pyr.plan(h, w, n)
         nlev, nb = self.height - 2, self.nbands
         sizes = plan.sizes
@@ -80,10 +86,13 @@ class Pyramid:
         c = n // f
         if c * f != n:
             raise VfiLibraryError("concat_frames must divide the number of images")
-        # block-input buffers [feature 64 | prediction P | phase f*nb | amp f*nb], P = 1 at the coarsest level
+        p_coarsest, p_band = (1, 8) if pred_channels is None else (int(pred_channels[0]), int(pred_channels[1]))
+        if p_coarsest < 1 or p_band < 1:
+            raise VfiLibraryError(f"pred_channels must be positive, got {pred_channels}")
+        # block-input buffers [feature 64 | prediction P | phase f*nb | amp f*nb], P = p_coarsest at the coarsest level
         bufs, phase, amp, table = [], [], [], []
         for k in range(nlev):
-            p_prev = 1 if k == nlev - 1 else 8
+            p_prev = p_coarsest if k == nlev - 1 else p_band
             ctot = 64 + p_prev + 2 * f * nb
             buf = new(c, ctot, *sizes[k])
             bufs.append(buf)

@@ -284,6 +284,31 @@ int vfi_phasenet_predict(const float *feat, long long feat_bstride, const float 
 int vfi_phasenet_emit_low(const float *pred, long long pred_bstride, const float *low_in, long long low_bstride,
                           const float *max_low, float *low_out, int N, int HW, vfi_stream_t stream);
 
+/* The three entry points above for PhaseNet with num_img = 2, 3 or 4 input images (the fusion variants of
+ * src/phase_net/phase_net.py:21-35: four images = the two frames and AdaCoF's two warped sides, three = the two frames and
+ * AdaCoF's result).  num_img = 2 gives the bits of the entry points above; any other value is VFI_ERR_UNSUPPORTED.
+ *
+ * vfi_phasenet_emit_n (phase_net.py:155-168 + :80-90): amp_in (N,4*num_img,HW); pred (N,8,HW), or (N,12,HW) for num_img = 3.
+ * The first blend as in vfi_phasenet_emit; for num_img = 3 then a second one (phase_net.py:158-162):
+ *   amp = fb*amp + (1-fb)*amp_in[:,8:12], fb = (pred[:,8:12]+1)/2, before the multiplication by max_amp[n].
+ * For num_img = 4 the planes 8..15 of amp_in are never read (phase_net.py:156). */
+int vfi_phasenet_emit_n(const float *pred, long long pred_bstride, const float *amp_in, long long amp_bstride,
+                        const float *max_amp, float *phase_out, float *amp_out, int N, int HW, int num_img, vfi_stream_t stream);
+
+/* vfi_phasenet_predict for num_img images (phase_net.py:149-168, 190-207): the prediction map is 64 -> 8, or 64 -> 12 for
+ * num_img = 3 (packed_w / bias of vfi_conv2d_pack for that Cout, KS = 1); pred (N,8 or 12,H*W), amp_in (N,4*num_img,H*W).  Same
+ * results as vfi_conv2d(act = tanh) followed by vfi_phasenet_emit_n -- bit for bit where both stream -- which is what small or
+ * odd-sized levels run. */
+int vfi_phasenet_predict_n(const float *feat, long long feat_bstride, const float *packed_w, const float *bias,
+                           const float *amp_in, long long amp_bstride, const float *max_amp, float *pred, long long pred_bstride,
+                           float *phase_out, float *amp_out, int N, int Cin, int H, int W, int num_img, vfi_stream_t stream);
+
+/* vfi_phasenet_emit_low for num_img images (phase_net.py:113-121 + :96-98): low_in (N,num_img,HW); pred (N,1,HW), or (N,2,HW)
+ * for num_img = 3, where low = fa*low + (1-fa)*low_in[:,2], fa = (pred[:,1]+1)/2, follows the first blend.  For num_img = 4
+ * the planes 2 and 3 of low_in are never read. */
+int vfi_phasenet_emit_low_n(const float *pred, long long pred_bstride, const float *low_in, long long low_bstride,
+                            const float *max_low, float *low_out, int N, int HW, int num_img, vfi_stream_t stream);
+
 /* FusionNet tail (fusion_net.py:70-77): y = clamp(base + tanh(x), 0, 1) over `count` floats. */
 int vfi_tanh_residual_clamp(const float *x, const float *base, float *y, long long count, vfi_stream_t stream);
 
