@@ -312,13 +312,13 @@ def conv2d_backward_data(dy, pct, pad_mode="zeros", out=None):
         out = new((n, cin, h, w), dy)
     elif tuple(out.shape) != (n, cin, h, w):
         raise VfiLibraryError(f"conv2d_backward_data: out shape {tuple(out.shape)} != {(n, cin, h, w)}")
+    gp, gs = _slice_ptr(dy, "dy")          # (before the workspace: a CPU tensor has no stream to key one on)
+    op, os_ = _slice_ptr(out, "out")
     need = _lib.lib().vfi_conv2d_backward_data_workspace_floats(n, cin, h, w, cout, ks, PAD[pad_mode])
     if need < 0:
         raise VfiLibraryError(f"conv2d_backward_data: unsupported layer {cout}->{cin} KS={ks}")
     ws = _workspace(dy.device) if need == 0 else torch.empty(need + BWD_DATA_SPLITK_FLOATS, dtype=torch.float32,
                                                              device=dy.device)
-    gp, gs = _slice_ptr(dy, "dy")
-    op, os_ = _slice_ptr(out, "out")
     work = None
     if _lib.PROFILE is not None:
         p = (ks - 1) // 2 if pad_mode == "reflect" else 0
