@@ -380,6 +380,26 @@ extern "C" int vfi_pyr_plan_level_size(const vfi_pyr_plan *p, int level, int *h,
     return VFI_OK;
 }
 
+// what resolve_level / resolve_size stored for one pass of one size: nothing is looked up again and nothing is launched
+extern "C" int vfi_pyr_plan_query_pass(const vfi_pyr_plan *p, int size_index, int pass, int *info) {
+    VFI_REQUIRE(p && info, VFI_ERR_INVALID_ARG, "vfi_pyr_plan_query_pass: null pointer");
+    VFI_REQUIRE(size_index >= 0 && size_index <= p->nlev + 1, VFI_ERR_INVALID_ARG, "vfi_pyr_plan_query_pass: size index %d", size_index);
+    const bool band = size_index < p->nlev;
+    VFI_REQUIRE(pass == VFI_PYR_PASS_ROWS || pass == VFI_PYR_PASS_ANA_COLS || (pass == VFI_PYR_PASS_SYN_COLS && band), VFI_ERR_INVALID_ARG,
+                "vfi_pyr_plan_query_pass: pass %d of size index %d", pass, size_index);
+    const Size2D &z = band ? static_cast<const Size2D &>(p->lev[size_index]) : (size_index == p->nlev ? p->low : p->frame);
+    const vfi::fft::Plan1D &pl = pass == VFI_PYR_PASS_ROWS ? z.pw : z.ph;
+    static_assert((int)kWaveRows == VFI_PYR_PASS_ROWS && (int)kWaveAnaCols == VFI_PYR_PASS_ANA_COLS && (int)kWaveSynCols == VFI_PYR_PASS_SYN_COLS,
+                  "VFI_PYR_PASS_* index Size2D::wave");
+    info[0] = pl.n; info[1] = pl.bluestein ? 1 : 0; info[2] = pl.m; info[3] = z.wave[pass].M;
+    info[4] = info[5] = info[6] = info[7] = 0;
+    if (band) {
+        const Level &L = p->lev[size_index];
+        info[4] = L.tile; info[5] = L.bands; info[6] = L.tpitch_ana; info[7] = L.tpitch_syn;
+    }
+    return VFI_OK;
+}
+
 // A_k[b] = lo0 * prod_{j<k} lomask_j * himask_k * two-sided angle mask b on level k's window (unshifted order): P_a with the
 // synthesis' angle masks.  The synthesis is real-linear in the band coefficients z_{k,b}; its adjoint applied to a gradient
 // image g is  grad z_{k,b} = 1/(H W) * IFFT2_k,unnormalised( i * window_k(FFT2(g)) * A_k[b] )  -- an analysis level with

@@ -995,6 +995,13 @@ extern "C" int vfi_pyr_apply_filter_pair(vfi_pyr_plan *p, int filter_a, const fl
     return vfi::check_launch("vfi_pyr_apply_filter_pair");
 }
 
+extern "C" int vfi_pyr_plan_multi_levels(const vfi_pyr_plan *p, int N, unsigned long long level_mask, unsigned long long *multi_mask) {
+    VFI_REQUIRE(p && multi_mask, VFI_ERR_INVALID_ARG, "vfi_pyr_plan_multi_levels: null pointer");
+    VFI_REQUIRE(N >= 1 && N <= p->max_images, VFI_ERR_INVALID_ARG, "vfi_pyr_plan_multi_levels: N=%d (plan max %d)", N, p->max_images);
+    *multi_mask = multi_levels(p, N, level_mask);
+    return VFI_OK;
+}
+
 extern "C" int vfi_pyr_analyze(vfi_pyr_plan *p, const float *img, int N, float *high, float *const *phase,
                                float *const *amp, const int *plane_index, float *low, float phase_scale,
                                unsigned long long level_mask, int flags, vfi_stream_t stream) {

@@ -60,6 +60,8 @@ SIGNATURES = {
     "vfi_pyr_plan_create": [c_i, c_i, c_i, c_i, c_d, c_i, ctypes.POINTER(ctypes.c_void_p)],
     "vfi_pyr_plan_destroy": [ctypes.c_void_p],
     "vfi_pyr_plan_level_size": [ctypes.c_void_p, c_i, ctypes.POINTER(c_i), ctypes.POINTER(c_i)],
+    "vfi_pyr_plan_query_pass": [ctypes.c_void_p, c_i, c_i, ctypes.POINTER(c_i)],
+    "vfi_pyr_plan_multi_levels": [ctypes.c_void_p, c_i, ctypes.c_ulonglong, ctypes.POINTER(ctypes.c_ulonglong)],
     "vfi_pyr_plan_prepare_filter": [ctypes.c_void_p, ctypes.c_ulonglong, c_i, c_i, ctypes.POINTER(c_i)],
     "vfi_pyr_apply_filter": [ctypes.c_void_p, c_i, c_f, c_i, c_f, c_s],
     "vfi_pyr_apply_filter_pair": [ctypes.c_void_p, c_i, c_f, c_i, c_f, c_i, c_f, c_s],

@@ -54,6 +54,21 @@ class Plan:
         except Exception:
             pass
 
+    PASSES = {"rows": 0, "ana_cols": 1, "syn_cols": 2}
+
+    def pass_info(self, size_index, which):
+        """How the plan runs one pass ("rows", "ana_cols", "syn_cols") of band level size_index, of the low residual
+        (size_index == height-2) or of the frame (height-1): vfi_pyr_plan_query_pass as a dict.  M == 0: the generic engine."""
+        info = (ctypes.c_int * 8)()
+        _lib.call("vfi_pyr_plan_query_pass", self._h, int(size_index), self.PASSES[which], info)
+        return dict(zip(("n", "bluestein", "m", "M", "tile", "bands", "tpitch_ana", "tpitch_syn"), info))
+
+    def multi_levels(self, n, mask):
+        """The levels of `mask` that an analysis of n images batches onto the generic engine (vfi_pyr_plan_multi_levels)."""
+        out = ctypes.c_ulonglong()
+        _lib.call("vfi_pyr_plan_multi_levels", self._h, int(n), int(mask), ctypes.byref(out))
+        return out.value
+
     def _bytes(self, n, mask, high, low):
         """Algorithmic HBM bytes of one transform: image + kept band planes (phase, amp) + residuals."""
         px = self.h * self.w + (self.h * self.w if high else 0) + (self.sizes[-1][0] * self.sizes[-1][1] if low else 0)

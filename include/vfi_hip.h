@@ -567,6 +567,23 @@ int vfi_pyr_plan_destroy(vfi_pyr_plan *plan);
  * ceil(H / scale_factor^level) x ceil(W / scale_factor^level). */
 int vfi_pyr_plan_level_size(const vfi_pyr_plan *plan, int level, int *h, int *w);
 
+/* Read-only queries of what a plan will do (no GPU call; for tests and profiling labels: the selection rules live in the
+ * library only, as with vfi_conv2d_algo).
+ * vfi_pyr_plan_query_pass: how one pass of one 2-D size runs, as the plan resolved it at creation.
+ *   size_index  band level 0 .. height-3, height-2 = the low residual, height-1 = the frame
+ *   pass        VFI_PYR_PASS_ROWS, VFI_PYR_PASS_ANA_COLS (also the plain column pass of the low residual's and the frame's
+ *               transforms), VFI_PYR_PASS_SYN_COLS (band levels only)
+ *   info        8 ints: [0] transform length n, [1] 1 when n goes through Bluestein, [2] the length m that is transformed
+ *               (n, or Bluestein's 2^k / 3*2^k), [3] wave-engine length M of the pass, 0 = the generic LDS engine runs it,
+ *               and for band levels (0 otherwise) [4] columns per workgroup and [5] bands per transform call of the generic
+ *               column kernels, [6] / [7] row pitch of the half-transformed array in the analysis / synthesis direction.
+ * vfi_pyr_plan_multi_levels: the levels of level_mask that an analysis (vfi_pyr_analyze, vfi_pyr_analyze_max,
+ * vfi_pyr_synthesize_backward) of N images runs in the batched launches of the small levels on the generic engine instead
+ * of their own passes; 0 when every level runs its own. */
+enum { VFI_PYR_PASS_ROWS = 0, VFI_PYR_PASS_ANA_COLS = 1, VFI_PYR_PASS_SYN_COLS = 2 };
+int vfi_pyr_plan_query_pass(const vfi_pyr_plan *plan, int size_index, int pass, int *info);
+int vfi_pyr_plan_multi_levels(const vfi_pyr_plan *plan, int N, unsigned long long level_mask, unsigned long long *multi_mask);
+
 /* Analysis followed by synthesis of an UNMODIFIED subset of the pyramid is a real, radially symmetric linear
  * filter (the four orientation masks form a partition of unity):
  *   inv_filter(keep(filter(x))) = real(ifft2(fft2(x) * G)),
