@@ -1,7 +1,7 @@
 // Backward of one PhaseNet level (gfx950): the HBM-bound adjoints between the existing convolution gradients
 // (vfi_conv_grad.hip).  Differentiates reference src/phase_net/phase_net.py:138-139 (bilinear resize to an arbitrary size),
 // :190-200 (ELU, tanh), :113-116 and :155-168 with reverse_normalize :80-98 (the per-level blends; a band level's whole
-// head in one pass), and
+// head in one pass; :119-121 and :158-162, the second blends of the network of three input images), and
 // src/train/loss.py:10-20 (phase loss, L1: AbsTerm over the shared two-stage reduction).  The rules: vfi_grad_common.h;
 // fp32 throughout.
 #include "vfi_grad_common.h"
@@ -83,6 +83,90 @@ __global__ void emit_low_backward_kernel(const float *__restrict__ g_low, const 
         const int p = i % HW, n = i / HW;
         const float *l = low + (size_t)n * low_bs + p;
         g_pred[(size_t)n * gp_bs + p] = g_low[i] * maxv[n] * (l[0] - l[HW]) * 0.5f;
+    }
+}
+
+// ---- the same adjoints for the network of three input images (vfi_phasenet_emit_n, vfi_phasenet_emit_low_n) ----------------
+// The forward blends twice (phase_net.py:158-162): amp1 = b a[4:8] + (1 - b) a[0:4], amp = fb amp1 + (1 - fb) a[8:12] with
+// b = (pred[4:8] + 1) / 2, fb = (pred[8:12] + 1) / 2, so pred is an input here:
+// g_pred[0:4] = pi g_phase,  g_pred[4:8] = g_amp max[n] fb (a[4:8] - a[0:4]) / 2,  g_pred[8:12] = g_amp max[n] (amp1 - a[8:12]) / 2.
+// One thread per (sample, band, group of VEC pixels); HW and the strides are in floats, HW a multiple of VEC.
+template <int VEC> struct GradVec;
+template <> struct GradVec<1> { typedef float type; };
+template <> struct GradVec<4> { typedef float4 type; };
+
+template <int VEC>
+__global__ void emit_fuse_backward_kernel(const float *__restrict__ g_phase, const float *__restrict__ g_amp,
+                                          const float *__restrict__ pred, long long pred_bs, const float *__restrict__ amp_in,
+                                          long long amp_bs, const float *__restrict__ maxv, float *__restrict__ g_pred,
+                                          long long gp_bs, int N, int HW) {
+    typedef typename GradVec<VEC>::type vec;
+    const int PG = HW / VEC;
+    GRID_STRIDE(i, (long long)N * 4 * PG) {
+        const int p = (int)(i % PG) * VEC, b = (i / PG) % 4, n = i / ((long long)PG * 4);
+        const size_t dense = ((size_t)n * 4 + b) * HW + p;
+        float *gp = g_pred + (size_t)n * gp_bs + p;
+        vec r0, r1, r2;
+        if (g_phase) {
+            const vec g = *reinterpret_cast<const vec *>(g_phase + dense);
+#pragma unroll
+            for (int v = 0; v < VEC; ++v) lane_set(r0, v, lane_get(g, v) * 3.14159265358979323846f);
+        } else {
+#pragma unroll
+            for (int v = 0; v < VEC; ++v) lane_set(r0, v, 0.0f);
+        }
+        if (g_amp) {
+            const float *am = amp_in + (size_t)n * amp_bs + p, *pr = pred + (size_t)n * pred_bs + p;
+            const vec g = *reinterpret_cast<const vec *>(g_amp + dense);
+            const vec a0 = *reinterpret_cast<const vec *>(am + (size_t)b * HW), a1 = *reinterpret_cast<const vec *>(am + (size_t)(4 + b) * HW);
+            const vec a2 = *reinterpret_cast<const vec *>(am + (size_t)(8 + b) * HW);
+            const vec p1 = *reinterpret_cast<const vec *>(pr + (size_t)(4 + b) * HW), p2 = *reinterpret_cast<const vec *>(pr + (size_t)(8 + b) * HW);
+            const float mx = maxv[n];
+#pragma unroll
+            for (int v = 0; v < VEC; ++v) {
+                const float beta = (lane_get(p1, v) + 1.0f) / 2.0f, fb = (lane_get(p2, v) + 1.0f) / 2.0f;
+                const float amp1 = fmaf(beta, lane_get(a1, v), (1.0f - beta) * lane_get(a0, v));      // the forward's own first blend
+                const float gm = lane_get(g, v) * mx;
+                lane_set(r1, v, gm * fb * (lane_get(a1, v) - lane_get(a0, v)) * 0.5f);
+                lane_set(r2, v, gm * (amp1 - lane_get(a2, v)) * 0.5f);
+            }
+        } else {
+#pragma unroll
+            for (int v = 0; v < VEC; ++v) { lane_set(r1, v, 0.0f); lane_set(r2, v, 0.0f); }
+        }
+        *reinterpret_cast<vec *>(gp + (size_t)b * HW) = r0;
+        *reinterpret_cast<vec *>(gp + (size_t)(4 + b) * HW) = r1;
+        *reinterpret_cast<vec *>(gp + (size_t)(8 + b) * HW) = r2;
+    }
+}
+// low1 = a l0 + (1 - a) l1, low = (fa low1 + (1 - fa) l2) max[n], a = (pred[0] + 1) / 2, fa = (pred[1] + 1) / 2:
+// g_pred[0] = g max[n] fa (l0 - l1) / 2,  g_pred[1] = g max[n] (low1 - l2) / 2
+template <int VEC>
+__global__ void emit_low_fuse_backward_kernel(const float *__restrict__ g_low, const float *__restrict__ pred, long long pred_bs,
+                                              const float *__restrict__ low, long long low_bs, const float *__restrict__ maxv,
+                                              float *__restrict__ g_pred, long long gp_bs, int N, int HW) {
+    typedef typename GradVec<VEC>::type vec;
+    const int PG = HW / VEC;
+    GRID_STRIDE(i, (long long)N * PG) {
+        const int p = (int)(i % PG) * VEC, n = i / PG;
+        const float *l = low + (size_t)n * low_bs + p, *pr = pred + (size_t)n * pred_bs + p;
+        const vec g = *reinterpret_cast<const vec *>(g_low + (size_t)n * HW + p);
+        const vec l0 = *reinterpret_cast<const vec *>(l), l1 = *reinterpret_cast<const vec *>(l + HW);
+        const vec l2 = *reinterpret_cast<const vec *>(l + (size_t)2 * HW);
+        const vec p0 = *reinterpret_cast<const vec *>(pr), p1 = *reinterpret_cast<const vec *>(pr + HW);
+        const float mx = maxv[n];
+        vec r0, r1;
+#pragma unroll
+        for (int v = 0; v < VEC; ++v) {
+            const float alpha = (lane_get(p0, v) + 1.0f) / 2.0f, fa = (lane_get(p1, v) + 1.0f) / 2.0f;
+            const float low1 = alpha * lane_get(l0, v) + (1.0f - alpha) * lane_get(l1, v);
+            const float gm = lane_get(g, v) * mx;
+            lane_set(r0, v, gm * fa * (lane_get(l0, v) - lane_get(l1, v)) * 0.5f);
+            lane_set(r1, v, gm * (low1 - lane_get(l2, v)) * 0.5f);
+        }
+        float *gp = g_pred + (size_t)n * gp_bs + p;
+        *reinterpret_cast<vec *>(gp) = r0;
+        *reinterpret_cast<vec *>(gp + HW) = r1;
     }
 }
 
@@ -243,6 +327,168 @@ __global__ __launch_bounds__(kThreads) void head_reduce_kernel(const float *__re
         for (int b = 0; b < blocks; ++b) v += part[(size_t)b * kHeadOut + o];
         if (o < 512) { if (g_w) g_w[o] = v; }
         else if (g_b) g_b[o - 512] = v;
+    }
+}
+
+// ---- the head's adjoint for three input images (vfi_phasenet_predict_n: 1x1 64 -> 12, tanh, both blends) --------------------
+// head_backward_kernel's sibling with twelve rows: the same block, tiles, phases and orders.  A1 forms gz of 12 rows (the
+// emit adjoint is emit_fuse_backward_kernel's), A2 reads a [k][12] weight image as three float4 per k, and in B each of the four
+// waves owns three rows of grad_W.  A block partial is grad_W (12, 64) then grad_b (12).
+constexpr int kHeadRowsN = 12;
+constexpr int kHeadOutN = kHeadRowsN * 64 + kHeadRowsN;
+static_assert(kMaxPartials * kHeadOutN <= VFI_PHASENET_HEAD_N_WORKSPACE_FLOATS, "head workspace (three images)");
+
+template <int VEC, bool WGRAD>
+__global__ __launch_bounds__(kThreads) void head_backward_fuse_kernel(HeadArgs a) {
+    typedef typename HeadVec<VEC>::type vec;
+    constexpr int R = kHeadRowsN;
+    constexpr int PG = kHeadTile / VEC;         // pixel groups per tile
+    constexpr int KPT = 64 / (kThreads / PG);   // feature channels per thread in A2
+    __shared__ __attribute__((aligned(16))) float s_f[WGRAD ? 64 * kHeadRow : 4];
+    __shared__ __attribute__((aligned(16))) float s_gz[R * kHeadTile];
+    __shared__ __attribute__((aligned(16))) float s_w[64 * R];      // [k][j]
+    const int t = threadIdx.x;
+    for (int i = t; i < 64 * R; i += kThreads) s_w[i] = a.w ? a.w[(i % R) * 64 + i / R] : 0.0f;
+    float acc[3] = {0.0f, 0.0f, 0.0f}, accb[3] = {0.0f, 0.0f, 0.0f};
+    const int HW = a.HW;
+    const long long tiles = (long long)a.N * a.tiles_per_sample;
+    for (long long tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
+        const int n = (int)(tile / a.tiles_per_sample);
+        const int px0 = (int)(tile - (long long)n * a.tiles_per_sample) * kHeadTile;
+        __syncthreads();        // the previous tile's B has read s_f and s_gz (first tile: s_w is written)
+        // A1
+        for (int e = t; e < R * PG; e += kThreads) {
+            const int j = e / PG, pg = e - j * PG, q = px0 + pg * VEC;
+            vec gz;
+            if (q < HW) {
+                const float *pr = a.pred + (size_t)n * a.pred_bs + q;
+                const vec y = *reinterpret_cast<const vec *>(pr + (size_t)j * HW);
+                vec g;
+#pragma unroll
+                for (int v = 0; v < VEC; ++v) lane_set(g, v, 0.0f);
+                if (j < 4) {
+                    if (a.g_phase) {
+                        const vec gp = *reinterpret_cast<const vec *>(a.g_phase + ((size_t)n * 4 + j) * HW + q);
+#pragma unroll
+                        for (int v = 0; v < VEC; ++v) lane_set(g, v, lane_get(gp, v) * 3.14159265358979323846f);
+                    }
+                } else if (a.g_amp) {
+                    const int b = j & 3;
+                    const float *am = a.amp + (size_t)n * a.amp_bs + q;
+                    const vec ga = *reinterpret_cast<const vec *>(a.g_amp + ((size_t)n * 4 + b) * HW + q);
+                    const vec a0 = *reinterpret_cast<const vec *>(am + (size_t)b * HW);
+                    const vec a1 = *reinterpret_cast<const vec *>(am + (size_t)(4 + b) * HW);
+                    const float mx = a.maxv[n];
+                    if (j < 8) {
+                        const vec p2 = *reinterpret_cast<const vec *>(pr + (size_t)(8 + b) * HW);
+#pragma unroll
+                        for (int v = 0; v < VEC; ++v) {
+                            const float fb = (lane_get(p2, v) + 1.0f) / 2.0f;
+                            lane_set(g, v, lane_get(ga, v) * mx * fb * (lane_get(a1, v) - lane_get(a0, v)) * 0.5f);
+                        }
+                    } else {
+                        const vec p1 = *reinterpret_cast<const vec *>(pr + (size_t)(4 + b) * HW);
+                        const vec a2 = *reinterpret_cast<const vec *>(am + (size_t)(8 + b) * HW);
+#pragma unroll
+                        for (int v = 0; v < VEC; ++v) {
+                            const float beta = (lane_get(p1, v) + 1.0f) / 2.0f;
+                            const float amp1 = fmaf(beta, lane_get(a1, v), (1.0f - beta) * lane_get(a0, v));
+                            lane_set(g, v, lane_get(ga, v) * mx * (amp1 - lane_get(a2, v)) * 0.5f);
+                        }
+                    }
+                }
+                if (a.g_pred) {
+                    const vec gi = *reinterpret_cast<const vec *>(a.g_pred + (size_t)n * a.gp_bs + (size_t)j * HW + q);
+#pragma unroll
+                    for (int v = 0; v < VEC; ++v) lane_set(g, v, lane_get(g, v) + lane_get(gi, v));
+                }
+#pragma unroll
+                for (int v = 0; v < VEC; ++v) lane_set(gz, v, lane_get(g, v) * (1.0f - lane_get(y, v) * lane_get(y, v)));
+            } else {
+#pragma unroll
+                for (int v = 0; v < VEC; ++v) lane_set(gz, v, 0.0f);
+            }
+            *reinterpret_cast<vec *>(s_gz + j * kHeadTile + pg * VEC) = gz;
+        }
+        __syncthreads();
+        // A2
+        {
+            const int pg = t % PG, k0 = (t / PG) * KPT, q = px0 + pg * VEC;
+            const bool valid = q < HW;
+            vec gz[R];
+#pragma unroll
+            for (int j = 0; j < R; ++j) gz[j] = *reinterpret_cast<const vec *>(s_gz + j * kHeadTile + pg * VEC);
+#pragma unroll 4
+            for (int kk = 0; kk < KPT; ++kk) {
+                const int k = k0 + kk;
+                if (WGRAD) {
+                    vec fv;
+#pragma unroll
+                    for (int v = 0; v < VEC; ++v) lane_set(fv, v, 0.0f);
+                    if (valid) fv = *reinterpret_cast<const vec *>(a.f + (size_t)n * a.f_bs + (size_t)k * HW + q);
+                    *reinterpret_cast<vec *>(s_f + k * kHeadRow + pg * VEC) = fv;
+                }
+                if (a.g_f && valid) {
+                    const float4 *wk = reinterpret_cast<const float4 *>(s_w + k * R);
+                    const float4 w0 = wk[0], w1 = wk[1], w2 = wk[2];
+                    vec r;
+#pragma unroll
+                    for (int v = 0; v < VEC; ++v) {
+                        float s = w0.x * lane_get(gz[0], v);
+                        s = fmaf(w0.y, lane_get(gz[1], v), s);
+                        s = fmaf(w0.z, lane_get(gz[2], v), s);
+                        s = fmaf(w0.w, lane_get(gz[3], v), s);
+                        s = fmaf(w1.x, lane_get(gz[4], v), s);
+                        s = fmaf(w1.y, lane_get(gz[5], v), s);
+                        s = fmaf(w1.z, lane_get(gz[6], v), s);
+                        s = fmaf(w1.w, lane_get(gz[7], v), s);
+                        s = fmaf(w2.x, lane_get(gz[8], v), s);
+                        s = fmaf(w2.y, lane_get(gz[9], v), s);
+                        s = fmaf(w2.z, lane_get(gz[10], v), s);
+                        s = fmaf(w2.w, lane_get(gz[11], v), s);
+                        lane_set(r, v, s);
+                    }
+                    *reinterpret_cast<vec *>(a.g_f + (size_t)n * a.gf_bs + (size_t)k * HW + q) = r;
+                }
+            }
+        }
+        if (WGRAD) {
+            __syncthreads();
+            // B
+            const int k = t & 63, j0 = 3 * (t >> 6);
+            const float4 *fr = reinterpret_cast<const float4 *>(s_f + k * kHeadRow);
+            const float4 *g0 = reinterpret_cast<const float4 *>(s_gz + j0 * kHeadTile);
+#pragma unroll 4
+            for (int p = 0; p < kHeadTile / 4; ++p) {
+                const float4 fv = fr[p];
+#pragma unroll
+                for (int r = 0; r < 3; ++r) {
+                    const float4 u = g0[r * (kHeadTile / 4) + p];
+                    acc[r] = fmaf(u.x, fv.x, acc[r]); acc[r] = fmaf(u.y, fv.y, acc[r]); acc[r] = fmaf(u.z, fv.z, acc[r]); acc[r] = fmaf(u.w, fv.w, acc[r]);
+                    accb[r] += u.x; accb[r] += u.y; accb[r] += u.z; accb[r] += u.w;
+                }
+            }
+        }
+    }
+    if (WGRAD) {
+        float *out = a.part + (size_t)blockIdx.x * kHeadOutN;
+        const int k = t & 63, j0 = 3 * (t >> 6);
+#pragma unroll
+        for (int r = 0; r < 3; ++r) {
+            out[(j0 + r) * 64 + k] = acc[r];
+            if (k == 0) out[R * 64 + j0 + r] = accb[r];
+        }
+    }
+}
+
+// stage 2 of the twelve-row head (one block), as head_reduce_kernel
+__global__ __launch_bounds__(kThreads) void head_reduce_fuse_kernel(const float *__restrict__ part, int blocks, float *__restrict__ g_w,
+                                                                    float *__restrict__ g_b) {
+    for (int o = threadIdx.x; o < kHeadOutN; o += kThreads) {
+        float v = 0.0f;
+        for (int b = 0; b < blocks; ++b) v += part[(size_t)b * kHeadOutN + o];
+        if (o < kHeadRowsN * 64) { if (g_w) g_w[o] = v; }
+        else if (g_b) g_b[o - kHeadRowsN * 64] = v;
     }
 }
 
@@ -532,6 +778,89 @@ extern "C" int vfi_phasenet_predict_backward(const float *feat, long long feat_b
         else hipLaunchKernelGGL((head_backward_kernel<1, false>), dim3(blocks), dim3(kThreads), 0, s, a);
     }
     return vfi::check_launch("vfi_phasenet_predict_backward");
+}
+
+extern "C" int vfi_phasenet_emit_n_backward(const float *grad_phase, const float *grad_amp, const float *pred, long long pred_bstride,
+                                            const float *amp_in, long long amp_bstride, const float *max_amp, float *grad_pred,
+                                            long long gp_bstride, int N, int HW, int num_img, vfi_stream_t stream) {
+    VFI_REQUIRE((grad_phase || grad_amp) && grad_pred, VFI_ERR_INVALID_ARG, "vfi_phasenet_emit_n_backward: null pointer");
+    VFI_REQUIRE(!grad_amp || (amp_in && max_amp), VFI_ERR_INVALID_ARG, "vfi_phasenet_emit_n_backward: amplitudes missing");
+    VFI_REQUIRE(N > 0 && HW > 0, VFI_ERR_INVALID_ARG, "vfi_phasenet_emit_n_backward: bad sizes");
+    VFI_REQUIRE(num_img >= 2 && num_img <= 4, VFI_ERR_UNSUPPORTED, "vfi_phasenet_emit_n_backward: num_img %d (2, 3 or 4)", num_img);
+    if (num_img != 3) {         // the blend of two images, whatever follows them in amp_in
+        LAUNCH_1D(emit_backward_kernel, (long long)N * 4 * HW, stream, grad_phase, grad_amp, amp_in, amp_bstride, max_amp,
+                  grad_pred, gp_bstride, N, HW);
+        return vfi::check_launch("vfi_phasenet_emit_n_backward");
+    }
+    VFI_REQUIRE(!grad_amp || pred, VFI_ERR_INVALID_ARG, "vfi_phasenet_emit_n_backward: the second blend's adjoint needs pred");
+    const bool v4 = HW % 4 == 0 && aligned16(grad_pred) && gp_bstride % 4 == 0 && (!grad_phase || aligned16(grad_phase)) &&
+                    (!grad_amp || (aligned16(grad_amp) && aligned16(amp_in) && amp_bstride % 4 == 0 && aligned16(pred) && pred_bstride % 4 == 0));
+    if (v4) LAUNCH_1D(emit_fuse_backward_kernel<4>, (long long)N * HW, stream, grad_phase, grad_amp, pred, pred_bstride, amp_in,
+                      amp_bstride, max_amp, grad_pred, gp_bstride, N, HW);
+    else LAUNCH_1D(emit_fuse_backward_kernel<1>, (long long)N * 4 * HW, stream, grad_phase, grad_amp, pred, pred_bstride, amp_in,
+                   amp_bstride, max_amp, grad_pred, gp_bstride, N, HW);
+    return vfi::check_launch("vfi_phasenet_emit_n_backward");
+}
+
+extern "C" int vfi_phasenet_emit_low_n_backward(const float *grad_low, const float *pred, long long pred_bstride, const float *low_in,
+                                                long long low_bstride, const float *max_low, float *grad_pred, long long gp_bstride,
+                                                int N, int HW, int num_img, vfi_stream_t stream) {
+    VFI_REQUIRE(grad_low && low_in && max_low && grad_pred, VFI_ERR_INVALID_ARG, "vfi_phasenet_emit_low_n_backward: null pointer");
+    VFI_REQUIRE(N > 0 && HW > 0, VFI_ERR_INVALID_ARG, "vfi_phasenet_emit_low_n_backward: bad sizes");
+    VFI_REQUIRE(num_img >= 2 && num_img <= 4, VFI_ERR_UNSUPPORTED, "vfi_phasenet_emit_low_n_backward: num_img %d (2, 3 or 4)", num_img);
+    if (num_img != 3) {
+        LAUNCH_1D(emit_low_backward_kernel, (long long)N * HW, stream, grad_low, low_in, low_bstride, max_low, grad_pred,
+                  gp_bstride, N, HW);
+        return vfi::check_launch("vfi_phasenet_emit_low_n_backward");
+    }
+    VFI_REQUIRE(pred, VFI_ERR_INVALID_ARG, "vfi_phasenet_emit_low_n_backward: the second blend's adjoint needs pred");
+    const bool v4 = HW % 4 == 0 && aligned16(grad_low) && aligned16(pred) && pred_bstride % 4 == 0 && aligned16(low_in) &&
+                    low_bstride % 4 == 0 && aligned16(grad_pred) && gp_bstride % 4 == 0;
+    if (v4) LAUNCH_1D(emit_low_fuse_backward_kernel<4>, (long long)N * HW / 4, stream, grad_low, pred, pred_bstride, low_in, low_bstride,
+                      max_low, grad_pred, gp_bstride, N, HW);
+    else LAUNCH_1D(emit_low_fuse_backward_kernel<1>, (long long)N * HW, stream, grad_low, pred, pred_bstride, low_in, low_bstride,
+                   max_low, grad_pred, gp_bstride, N, HW);
+    return vfi::check_launch("vfi_phasenet_emit_low_n_backward");
+}
+
+extern "C" int vfi_phasenet_predict_n_backward(const float *feat, long long feat_bstride, const float *pred, long long pred_bstride,
+                                               const float *amp_in, long long amp_bstride, const float *max_amp, const float *weight,
+                                               const float *grad_phase, const float *grad_amp, const float *grad_pred_in,
+                                               long long gpi_bstride, float *grad_feat, long long gf_bstride, float *grad_weight,
+                                               float *grad_bias, float *workspace, int N, int HW, int num_img, vfi_stream_t stream) {
+    const bool wgrad = grad_weight || grad_bias;
+    VFI_REQUIRE(pred && (grad_feat || wgrad), VFI_ERR_INVALID_ARG, "vfi_phasenet_predict_n_backward: null pointer");
+    VFI_REQUIRE(!grad_feat || weight, VFI_ERR_INVALID_ARG, "vfi_phasenet_predict_n_backward: grad_feat needs the weights");
+    VFI_REQUIRE(!wgrad || (feat && workspace), VFI_ERR_INVALID_ARG, "vfi_phasenet_predict_n_backward: parameter gradients need feat and a workspace");
+    VFI_REQUIRE(!grad_amp || (amp_in && max_amp), VFI_ERR_INVALID_ARG, "vfi_phasenet_predict_n_backward: amplitudes missing");
+    VFI_REQUIRE(N > 0 && HW > 0, VFI_ERR_INVALID_ARG, "vfi_phasenet_predict_n_backward: bad sizes");
+    VFI_REQUIRE(num_img >= 2 && num_img <= 4, VFI_ERR_UNSUPPORTED, "vfi_phasenet_predict_n_backward: num_img %d (2, 3 or 4)", num_img);
+    if (num_img != 3)           // eight predictions, the blend of the first two images: the two-image head's own launches
+        return vfi_phasenet_predict_backward(feat, feat_bstride, pred, pred_bstride, amp_in, amp_bstride, max_amp, weight, grad_phase,
+                                             grad_amp, grad_pred_in, gpi_bstride, grad_feat, gf_bstride, grad_weight, grad_bias,
+                                             workspace, N, HW, stream);
+    VFI_REQUIRE(64ll * HW < (1ll << 31), VFI_ERR_UNSUPPORTED, "vfi_phasenet_predict_n_backward: per-sample tensor too large for 32-bit pixel indices");
+    HeadArgs a{};
+    a.f = feat; a.pred = pred; a.amp = amp_in; a.maxv = max_amp; a.w = weight; a.g_phase = grad_phase; a.g_amp = grad_amp;
+    a.g_pred = grad_pred_in; a.f_bs = feat_bstride; a.pred_bs = pred_bstride; a.amp_bs = amp_bstride; a.gp_bs = gpi_bstride;
+    a.gf_bs = gf_bstride; a.g_f = grad_feat; a.part = workspace; a.N = N; a.HW = HW;
+    a.tiles_per_sample = (HW + kHeadTile - 1) / kHeadTile;
+    const long long tiles = (long long)N * a.tiles_per_sample;
+    const int blocks = (int)(tiles < kMaxPartials ? tiles : kMaxPartials);
+    const bool v4 = HW % 4 == 0 && aligned16(pred) && pred_bstride % 4 == 0 && (!wgrad || (aligned16(feat) && feat_bstride % 4 == 0)) &&
+                    (!grad_feat || (aligned16(grad_feat) && gf_bstride % 4 == 0)) && (!grad_phase || aligned16(grad_phase)) &&
+                    (!grad_amp || (aligned16(grad_amp) && aligned16(amp_in) && amp_bstride % 4 == 0)) &&
+                    (!grad_pred_in || (aligned16(grad_pred_in) && gpi_bstride % 4 == 0));
+    hipStream_t s = vfi::as_stream(stream);
+    if (wgrad) {
+        if (v4) hipLaunchKernelGGL((head_backward_fuse_kernel<4, true>), dim3(blocks), dim3(kThreads), 0, s, a);
+        else hipLaunchKernelGGL((head_backward_fuse_kernel<1, true>), dim3(blocks), dim3(kThreads), 0, s, a);
+        hipLaunchKernelGGL(head_reduce_fuse_kernel, dim3(1), dim3(kThreads), 0, s, workspace, blocks, grad_weight, grad_bias);
+    } else {
+        if (v4) hipLaunchKernelGGL((head_backward_fuse_kernel<4, false>), dim3(blocks), dim3(kThreads), 0, s, a);
+        else hipLaunchKernelGGL((head_backward_fuse_kernel<1, false>), dim3(blocks), dim3(kThreads), 0, s, a);
+    }
+    return vfi::check_launch("vfi_phasenet_predict_n_backward");
 }
 
 extern "C" int vfi_l1_forward(const float *a, const float *b, long long count, int wrap, float scale, float *workspace,

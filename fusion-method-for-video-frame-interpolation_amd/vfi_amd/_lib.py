@@ -101,6 +101,9 @@ SIGNATURES = {
     "vfi_phasenet_emit_backward": [c_f, c_f, c_f, c_l, c_f, c_f, c_l, c_i, c_i, c_s],
     "vfi_phasenet_emit_low_backward": [c_f, c_f, c_l, c_f, c_f, c_l, c_i, c_i, c_s],
     "vfi_phasenet_predict_backward": [c_f, c_l] * 3 + [c_f] * 5 + [c_l, c_f, c_l, c_f, c_f, c_f, c_i, c_i, c_s],
+    "vfi_phasenet_emit_n_backward": [c_f, c_f, c_f, c_l, c_f, c_l, c_f, c_f, c_l, c_i, c_i, c_i, c_s],
+    "vfi_phasenet_emit_low_n_backward": [c_f, c_f, c_l, c_f, c_l, c_f, c_f, c_l, c_i, c_i, c_i, c_s],
+    "vfi_phasenet_predict_n_backward": [c_f, c_l] * 3 + [c_f] * 5 + [c_l, c_f, c_l, c_f, c_f, c_f, c_i, c_i, c_i, c_s],
     "vfi_bn_stats": [c_f, c_l, c_i, c_i, c_i, c_f, c_f, c_f, c_s],
     "vfi_bn_act_forward": [c_f, c_l, c_f, c_f, c_f, c_f, c_fl, c_i, c_f, c_l, c_i, c_i, c_i, c_s],
     "vfi_bn_act_backward": [c_f, c_l] * 3 + [c_f, c_f, c_f, c_fl, c_i, c_f, c_l, c_f, c_f, c_f, c_i, c_i, c_i, c_s],
@@ -109,6 +112,7 @@ SIGNATURES = {
 }
 REDUCE_WORKSPACE_FLOATS = 4096      # VFI_REDUCE_WORKSPACE_FLOATS
 PHASENET_HEAD_WORKSPACE_FLOATS = 1024 * 520     # VFI_PHASENET_HEAD_WORKSPACE_FLOATS
+PHASENET_HEAD_N_WORKSPACE_FLOATS = 1024 * 780   # VFI_PHASENET_HEAD_N_WORKSPACE_FLOATS (twelve predictions: three input images)
 # entry points that return a value instead of a vfi_status
 RESTYPES = {"vfi_conv2d_packed_floats": c_l, "vfi_conv2d_backward_weight_workspace_floats": c_l,
             "vfi_conv2d_backward_data_workspace_floats": c_l}

@@ -790,6 +790,96 @@ def phasenet_emit_low_backward(grad_low, low_in, max_low):
     return out
 
 
+# ---- the adjoints of the three heads above ----------------------------------------------------------
+def phasenet_emit_n_backward(grad_phase, grad_amp, pred, amp_in, max_amp, num_img, out=None):
+    """grad of phasenet_emit_n's pred (N,P,H,W) from the gradients of its outputs (either may be None = zero).  pred (the
+    forward's input) is read for three images only, by the second blend's adjoint; amp_in is passed whole (N,4*num_img,H,W).
+    `out`: where the gradient goes (a channel slice is fine)."""
+    p_band = phasenet_pred_channels(num_img)[1]
+    n, c, h, w = amp_in.shape
+    if c != 4 * num_img or tuple(pred.shape) != (n, p_band, h, w) or max_amp.numel() != n:
+        raise VfiLibraryError(f"phasenet_emit_n_backward: pred must be (N,{p_band},H,W), amp_in (N,{4 * num_img},H,W), max_amp (N,)")
+    if grad_phase is None and grad_amp is None:
+        raise VfiLibraryError("phasenet_emit_n_backward: no upstream gradient")
+    for g, name in ((grad_phase, "grad_phase"), (grad_amp, "grad_amp")):
+        if g is not None and g.numel() != n * 4 * h * w:
+            raise VfiLibraryError(f"phasenet_emit_n_backward: {name} shape mismatch")
+    if out is None:
+        out = new((n, p_band, h, w), amp_in)
+    elif tuple(out.shape) != (n, p_band, h, w):
+        raise VfiLibraryError(f"phasenet_emit_n_backward: out shape {tuple(out.shape)} != {(n, p_band, h, w)}")
+    pp, ps = _slice_ptr(pred, "pred")
+    ap, as_ = _slice_ptr(amp_in, "amp_in")
+    op, os_ = _slice_ptr(out, "out")
+    planes = p_band + 4 * (grad_phase is not None) + (4 + (20 if num_img == 3 else 8)) * (grad_amp is not None)
+    _lib.call("vfi_phasenet_emit_n_backward", _lib.dptr(grad_phase, "grad_phase"), _lib.dptr(grad_amp, "grad_amp"), pp, ps, ap, as_,
+              _lib.dptr(max_amp, "max_amp"), op, os_, n, h * w, num_img, _lib.stream_ptr(),
+              work=_prof("byte", 4.0 * n * h * w * planes, "phasenet_emit_n_backward"))
+    return out
+
+
+def phasenet_emit_low_n_backward(grad_low, pred, low_in, max_low, num_img, out=None):
+    """grad of phasenet_emit_low_n's pred (N,P,H,W), P = 2 for three images and 1 otherwise; low_in whole (N,num_img,H,W)."""
+    p_low = phasenet_pred_channels(num_img)[0]
+    n, c, h, w = low_in.shape
+    if c != num_img or tuple(pred.shape) != (n, p_low, h, w) or max_low.numel() != n:
+        raise VfiLibraryError(f"phasenet_emit_low_n_backward: pred must be (N,{p_low},H,W), low_in (N,{num_img},H,W), max_low (N,)")
+    if grad_low.numel() != n * h * w:
+        raise VfiLibraryError("phasenet_emit_low_n_backward: gradient shape mismatch")
+    if out is None:
+        out = new((n, p_low, h, w), low_in)
+    elif tuple(out.shape) != (n, p_low, h, w):
+        raise VfiLibraryError(f"phasenet_emit_low_n_backward: out shape {tuple(out.shape)} != {(n, p_low, h, w)}")
+    pp, ps = _slice_ptr(pred, "pred")
+    lp, ls = _slice_ptr(low_in, "low_in")
+    op, os_ = _slice_ptr(out, "out")
+    _lib.call("vfi_phasenet_emit_low_n_backward", _lib.dptr(grad_low, "grad_low"), pp, ps, lp, ls, _lib.dptr(max_low, "max_low"),
+              op, os_, n, h * w, num_img, _lib.stream_ptr(),
+              work=_prof("byte", 4.0 * n * h * w * (8 if num_img == 3 else 4), "phasenet_emit_low_n_backward"))
+    return out
+
+
+def phasenet_predict_n_backward(feat, pred, amp_in, max_amp, weight, num_img, grad_phase=None, grad_amp=None, grad_pred_in=None,
+                                need_feat=True, need_weight=True, need_bias=True, out=None):
+    """Adjoint of phasenet_predict_n in one pass (vfi_phasenet_predict_n_backward): phasenet_predict_backward's arguments and
+    results with P = 12 predictions for three images (8 otherwise) and amp_in passed whole (N,4*num_img,H,W):
+    -> (grad_feat (N,64,H,W), grad_weight (P,64,1,1), grad_bias (P,)), None where not needed."""
+    p_band = phasenet_pred_channels(num_img)[1]
+    n, cin, h, w = feat.shape
+    if cin != 64 or tuple(pred.shape) != (n, p_band, h, w) or tuple(weight.shape) != (p_band, 64, 1, 1):
+        raise VfiLibraryError(f"phasenet_predict_n_backward: feat (N,64,H,W), pred (N,{p_band},H,W), weight ({p_band},64,1,1)")
+    if not (need_feat or need_weight or need_bias):
+        raise VfiLibraryError("phasenet_predict_n_backward: no output asked for")
+    for g, name in ((grad_phase, "grad_phase"), (grad_amp, "grad_amp")):
+        if g is not None and g.numel() != n * 4 * h * w:
+            raise VfiLibraryError(f"phasenet_predict_n_backward: {name} shape mismatch")
+    if grad_pred_in is not None and tuple(grad_pred_in.shape) != (n, p_band, h, w):
+        raise VfiLibraryError("phasenet_predict_n_backward: grad_pred_in shape mismatch")
+    if grad_amp is not None and (tuple(amp_in.shape) != (n, 4 * num_img, h, w) or max_amp.numel() != n):
+        raise VfiLibraryError(f"phasenet_predict_n_backward: amp_in must be (N,{4 * num_img},H,W), max_amp (N,)")
+    fp, fs = _slice_ptr(feat, "feat")
+    pp, ps = _slice_ptr(pred, "pred")
+    ap, as_ = (None, 0) if grad_amp is None else _slice_ptr(amp_in, "amp_in")
+    ip, is_ = (None, 0) if grad_pred_in is None else _slice_ptr(grad_pred_in, "grad_pred_in")
+    gf = None
+    if need_feat:
+        gf = new((n, 64, h, w), feat) if out is None else out
+        if tuple(gf.shape) != (n, 64, h, w):
+            raise VfiLibraryError(f"phasenet_predict_n_backward: out shape {tuple(gf.shape)} != {(n, 64, h, w)}")
+    gp, gs = (None, 0) if gf is None else _slice_ptr(gf, "out")
+    gw = new((p_band, 64, 1, 1), feat) if need_weight else None
+    gb = new((p_band,), feat) if need_bias else None
+    floats = _lib.PHASENET_HEAD_N_WORKSPACE_FLOATS if num_img == 3 else _lib.PHASENET_HEAD_WORKSPACE_FLOATS
+    ws = torch.empty(floats, dtype=torch.float32, device=feat.device) if need_weight or need_bias else None
+    planes = p_band + 64 * (need_weight or need_bias) + 64 * need_feat + 4 * (grad_phase is not None) + \
+        (4 + (20 if num_img == 3 else 8)) * (grad_amp is not None) + p_band * (grad_pred_in is not None)
+    _lib.call("vfi_phasenet_predict_n_backward", fp, fs, pp, ps, ap, as_, _lib.dptr(max_amp, "max_amp") if grad_amp is not None else None,
+              _lib.dptr(weight.detach(), "weight"), _lib.dptr(grad_phase, "grad_phase"), _lib.dptr(grad_amp, "grad_amp"), ip, is_,
+              gp, gs, _lib.dptr(gw), _lib.dptr(gb), _lib.dptr(ws), n, h * w, num_img, _lib.stream_ptr(),
+              work=_prof("byte", 4.0 * n * h * w * planes, "phasenet_predict_n_backward"))
+    return gf, gw, gb
+
+
 def l1_forward(a, b, wrap=False, scale=1.0):
     """scale * mean |w(a - b)| -> 0-dim tensor; w = atan2(sin, cos) when wrap (the phase loss), else the identity."""
     if a.numel() != b.numel():

@@ -33,10 +33,12 @@ class PhaseNet(torch.nn.Module):
         """architecture.py:34-36 (map_location added: the reference file carries a cuda:0 storage tag)."""
         self.core.load_state_dict(torch.load(path, map_location="cpu"))
 
-    def fine_tune(self, mode=True, batch_stats=False):
+    def fine_tune(self, mode=True, batch_stats=False, fusion=False):
         """Training on or off (PhaseNetCore.fine_tune); off in a new module.  batch_stats=True: BatchNorm on the batch's
-        statistics with the running ones updated, the reference's training mode.  The module stays in eval mode either way."""
-        self.core.fine_tune(mode, batch_stats=batch_stats)
+        statistics with the running ones updated, the reference's training mode.  fusion=True: what a network of three or
+        four input images needs besides (the bare call keeps raising for them; see PhaseNetCore.fine_tune).  The module stays
+        in eval mode either way."""
+        self.core.fine_tune(mode, batch_stats=batch_stats, fusion=fusion)
         return self
 
     def forward(self, img_batch, high_level=False, ada_pred=None, m=None):

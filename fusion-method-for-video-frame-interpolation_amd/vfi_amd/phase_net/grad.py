@@ -17,6 +17,10 @@ The walk's own pieces, one band level (phase_net.py:138-168):
 A block whose `batch_stats` flag is set (PhaseNetBlock.batch_statistics, PhaseNet.fine_tune(batch_stats=True)) takes the
 batch-statistics route of section 17 in the same nodes: conv 1 with its raw weights, vfi_bn_stats, vfi_bn_act_forward, conv 2,
 and the running statistics updated at every forward, grad mode or not.  With the flag off nothing here changes.
+
+`level_head`, `blend_level`, `blend_low` and `head_backward_composed` take `num_img` (default 2: the calls above).  For the
+fusion networks of three and four input images (section 20) they go through the `_n` entry points and their adjoints, with
+the level's amplitudes and the low level passed whole (4 * num_img and num_img planes).
 """
 import torch
 
@@ -290,12 +294,20 @@ class _FeatureFunction(torch.autograd.Function):
 
 
 HEAD_ONE_PASS = True        # the head's backward: vfi_phasenet_predict_backward, or the five-launch composition (section 16)
+HEAD_ONE_PASS_THREE = True  # ... and whether the twelve-output head of three input images follows it (section 20's measurement)
 
 
-def head_backward_composed(f, c, amp_in, max_amp, weight, g_phase, g_amp, g_c, need_feat=True, need_weight=True, need_bias=True):
+def head_backward_composed(f, c, amp_in, max_amp, weight, g_phase, g_amp, g_c, need_feat=True, need_weight=True, need_bias=True,
+                           num_img=2):
     """The head's adjoint from the entry points of section 14: emit backward, (+ g_c), tanh backward, 1x1 weight gradient,
-    1x1 data gradient.  Same contract as ops.phasenet_predict_backward."""
-    g = ops.phasenet_emit_backward(g_phase, g_amp, amp_in, max_amp) if g_phase is not None or g_amp is not None else None
+    1x1 data gradient.  Same contract as ops.phasenet_predict_backward (ops.phasenet_predict_n_backward for num_img = 3, 4:
+    amp_in whole, the emit adjoint of section 20)."""
+    if g_phase is None and g_amp is None:
+        g = None
+    elif num_img == 2:
+        g = ops.phasenet_emit_backward(g_phase, g_amp, amp_in, max_amp)
+    else:
+        g = ops.phasenet_emit_n_backward(g_phase, g_amp, c, amp_in, max_amp, num_img)
     if g is None:
         g = g_c if g_c is not None else torch.zeros_like(c)
     elif g_c is not None:
@@ -309,42 +321,55 @@ def head_backward_composed(f, c, amp_in, max_amp, weight, g_phase, g_amp, g_c, n
     return gf, (gw if need_weight else None), gb
 
 
-def level_head(blk, f, amp_in, max_amp):
+def level_head(blk, f, amp_in, max_amp, num_img=2):
     """(c, phase_out, amp_out) of one band level from its features (phase_net.py:149-168 + reverse_normalize :80-90):
     c = blk.prediction_map(f) (N,8,H,W), the de-normalised outputs (N*4,1,H,W).  One vfi_phasenet_predict call, as in
-    inference; an autograd node with a one-pass backward when f or the head's parameters require grad."""
+    inference; an autograd node with a one-pass backward when f or the head's parameters require grad.  num_img = 3, 4 (the
+    fusion networks, section 20): amp_in whole (N,4*num_img,H,W), c (N,12,H,W) for three images, vfi_phasenet_predict_n and its
+    adjoint."""
     _check_eval(blk)
     pm = blk.prediction_map[0]
     if _wants_grad(f, pm.weight, pm.bias):
-        return _HeadFunction.apply(blk, f, amp_in.detach(), max_amp.detach(), pm.weight, pm.bias)
-    return ops.phasenet_predict(f, _forward_packs(blk)[2], amp_in, max_amp)
+        return _HeadFunction.apply(blk, f, amp_in.detach(), max_amp.detach(), pm.weight, pm.bias, num_img)
+    return _head_launch(blk, f, amp_in, max_amp, num_img)
+
+
+def _head_launch(blk, f, amp_in, max_amp, num_img):
+    if num_img == 2:
+        return ops.phasenet_predict(f, _forward_packs(blk)[2], amp_in, max_amp)
+    return ops.phasenet_predict_n(f, _forward_packs(blk)[2], amp_in, max_amp, num_img)
 
 
 class _HeadFunction(torch.autograd.Function):
-    """Inputs: (blk, f, amp_in, max_amp, wp, bp) -> (c, phase, amp).  c also feeds the next finer level, whose resize
-    adjoint arrives here as g_c."""
+    """Inputs: (blk, f, amp_in, max_amp, wp, bp, num_img) -> (c, phase, amp).  c also feeds the next finer level, whose
+    resize adjoint arrives here as g_c."""
 
     @staticmethod
-    def forward(ctx, blk, f, amp_in, max_amp, wp, bp):
-        c, phase, amp = ops.phasenet_predict(f, _forward_packs(blk)[2], amp_in, max_amp)
+    def forward(ctx, blk, f, amp_in, max_amp, wp, bp, num_img=2):
+        c, phase, amp = _head_launch(blk, f, amp_in, max_amp, num_img)
+        ctx.num_img = num_img
         ctx.save_for_backward(f, c, amp_in, max_amp, wp)
         ctx.set_materialize_grads(False)
         return c, phase, amp
 
     @staticmethod
     def backward(ctx, g_c, g_phase, g_amp):
-        need = ctx.needs_input_grad             # (blk, f, amp_in, max_amp, wp, bp)
+        need = ctx.needs_input_grad             # (blk, f, amp_in, max_amp, wp, bp, num_img)
         if (g_c is None and g_phase is None and g_amp is None) or not (need[1] or need[4] or need[5]):
-            return (None,) * 6
+            return (None,) * 7
         f, c, amp_in, max_amp, wp = ctx.saved_tensors
         cont = lambda g: g.contiguous() if g is not None else None
-        if HEAD_ONE_PASS:
+        num_img = ctx.num_img
+        if not (HEAD_ONE_PASS and (HEAD_ONE_PASS_THREE or num_img != 3)):
+            gf, gw, gb = head_backward_composed(f, c, amp_in, max_amp, wp, cont(g_phase), cont(g_amp), cont(g_c),
+                                                need_feat=need[1], need_weight=need[4], need_bias=need[5], num_img=num_img)
+        elif num_img == 2:
             gf, gw, gb = ops.phasenet_predict_backward(f, c, amp_in, max_amp, wp, cont(g_phase), cont(g_amp), cont(g_c),
                                                        need_feat=need[1], need_weight=need[4], need_bias=need[5])
         else:
-            gf, gw, gb = head_backward_composed(f, c, amp_in, max_amp, wp, cont(g_phase), cont(g_amp), cont(g_c),
-                                                need_feat=need[1], need_weight=need[4], need_bias=need[5])
-        return None, gf, None, None, gw, gb
+            gf, gw, gb = ops.phasenet_predict_n_backward(f, c, amp_in, max_amp, wp, num_img, cont(g_phase), cont(g_amp), cont(g_c),
+                                                         need_feat=need[1], need_weight=need[4], need_bias=need[5])
+        return None, gf, None, None, gw, gb, None
 
 
 def level_input(f, c, phase, amp):
@@ -406,44 +431,56 @@ def resize_bilinear(x, size):
 
 class _BlendLevel(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, pred, amp_in, max_amp):
-        ctx.save_for_backward(amp_in, max_amp)
+    def forward(ctx, pred, amp_in, max_amp, num_img=2):
+        ctx.num_img = num_img
+        ctx.save_for_backward(pred, amp_in, max_amp)
         ctx.set_materialize_grads(False)
-        return ops.phasenet_emit(pred, amp_in, max_amp)
+        if num_img == 2:
+            return ops.phasenet_emit(pred, amp_in, max_amp)
+        return ops.phasenet_emit_n(pred, amp_in, max_amp, num_img)
 
     @staticmethod
     def backward(ctx, g_phase, g_amp):
         if g_phase is None and g_amp is None:
-            return None, None, None
-        amp_in, max_amp = ctx.saved_tensors
+            return None, None, None, None
+        pred, amp_in, max_amp = ctx.saved_tensors
         c = lambda g: g.contiguous() if g is not None else None
-        return ops.phasenet_emit_backward(c(g_phase), c(g_amp), amp_in, max_amp), None, None
+        if ctx.num_img == 2:
+            return ops.phasenet_emit_backward(c(g_phase), c(g_amp), amp_in, max_amp), None, None, None
+        return ops.phasenet_emit_n_backward(c(g_phase), c(g_amp), pred, amp_in, max_amp, ctx.num_img), None, None, None
 
 
-def blend_level(pred, amp_in, max_amp):
+def blend_level(pred, amp_in, max_amp, num_img=2):
     """One band level's de-normalised outputs from its prediction map (phase_net.py:155-168 + reverse_normalize :80-90):
     pred (N,8,H,W), amp_in (N,8,H,W) the normalised input amplitudes, max_amp (N,) -> (phase, amp), each (N*4,1,H,W).
+    num_img = 3, 4: amp_in whole (N,4*num_img,H,W), pred (N,12,H,W) for three images (vfi_phasenet_emit_n and its adjoint).
     Differentiable in pred; amp_in and max_amp get no gradient."""
     if _wants_grad(pred):
-        return _BlendLevel.apply(pred, amp_in.detach(), max_amp.detach())
-    return ops.phasenet_emit(pred, amp_in, max_amp)
+        return _BlendLevel.apply(pred, amp_in.detach(), max_amp.detach(), num_img)
+    return ops.phasenet_emit(pred, amp_in, max_amp) if num_img == 2 else ops.phasenet_emit_n(pred, amp_in, max_amp, num_img)
 
 
 class _BlendLow(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, pred, low_in, max_low):
-        ctx.save_for_backward(low_in, max_low)
-        return ops.phasenet_emit_low(pred, low_in, max_low)
+    def forward(ctx, pred, low_in, max_low, num_img=2):
+        ctx.num_img = num_img
+        ctx.save_for_backward(pred, low_in, max_low)
+        if num_img == 2:
+            return ops.phasenet_emit_low(pred, low_in, max_low)
+        return ops.phasenet_emit_low_n(pred, low_in, max_low, num_img)
 
     @staticmethod
     def backward(ctx, g_low):
-        low_in, max_low = ctx.saved_tensors
-        return ops.phasenet_emit_low_backward(g_low.contiguous(), low_in, max_low), None, None
+        pred, low_in, max_low = ctx.saved_tensors
+        if ctx.num_img == 2:
+            return ops.phasenet_emit_low_backward(g_low.contiguous(), low_in, max_low), None, None, None
+        return ops.phasenet_emit_low_n_backward(g_low.contiguous(), pred, low_in, max_low, ctx.num_img), None, None, None
 
 
-def blend_low(pred, low_in, max_low):
+def blend_low(pred, low_in, max_low, num_img=2):
     """The low level's de-normalised output (phase_net.py:113-116 + :96-98): pred (N,1,H,W), low_in (N,2,H,W) normalised,
-    max_low (N,) -> (N,1,H,W).  Differentiable in pred."""
+    max_low (N,) -> (N,1,H,W).  num_img = 3, 4: low_in (N,num_img,H,W), pred (N,2,H,W) for three images.  Differentiable in
+    pred."""
     if _wants_grad(pred):
-        return _BlendLow.apply(pred, low_in.detach(), max_low.detach())
-    return ops.phasenet_emit_low(pred, low_in, max_low)
+        return _BlendLow.apply(pred, low_in.detach(), max_low.detach(), num_img)
+    return ops.phasenet_emit_low(pred, low_in, max_low) if num_img == 2 else ops.phasenet_emit_low_n(pred, low_in, max_low, num_img)

@@ -15,7 +15,7 @@ Maxima are returned/kept per call on the module (as the reference does, phase_ne
 
 `num_img` = 3 and 4 are the reference's pyramid-domain fusion networks (phase_net.py:21-35, 119-121, 158-162; DESIGN.md section
 18): the buffers are [feature 64 | prediction P | phase 4*num_img | amp 4*num_img] with P = `pred_channels`, the heads are
-vfi_phasenet_predict_n / vfi_phasenet_emit_low_n.  Inference only.
+vfi_phasenet_predict_n / vfi_phasenet_emit_low_n.  They train after `fine_tune(fusion=True)`.
 
 After `fine_tune()`, with grad mode on and a parameter of `layers` requiring grad, `forward` takes a second route,
 `_forward_grad`: the same walk as an autograd graph with HIP backward kernels, BatchNorm on its running statistics (DESIGN.md
@@ -92,16 +92,23 @@ class PhaseNet(PackedModule):
         what Pyramid.filter(concat_frames=num_img, pred_channels=...) lays the block-input buffers out for."""
         return ops.phasenet_pred_channels(self.num_img)
 
-    def fine_tune(self, mode=True, batch_stats=False):
+    def fine_tune(self, mode=True, batch_stats=False, fusion=False):
         """Training on or off (off in a new module).  It is PhaseNet's counterpart of FusionNet's training mode: a new
         module's parameters require grad, so callers that never backpropagate keep results without a grad_fn unless they
         ask here.  `fine_tune()` is fixed-statistics fine-tuning: BatchNorm on the running statistics of the checkpoint.
         `fine_tune(batch_stats=True)` is the reference's training mode (src/train/train.py:90, trainer.py:107-134): it sets
         every block's `batch_stats` flag, and every forward from then on, grad mode or not, normalises with the batch's
-        statistics and moves the running ones.  `fine_tune(False)` clears both.  The module stays in eval mode throughout
-        (`training` is False); `train(True)` keeps raising.  The networks of three and four input images run inference only."""
-        if mode and self.num_img != 2:
-            raise NotImplementedError("training of the fusion variants (num_img = 3, 4) is not built: PhaseNet.fine_tune needs num_img = 2")
+        statistics and moves the running ones.  `fine_tune(False)` clears everything.  The module stays in eval mode throughout
+        (`training` is False); `train(True)` keeps raising.
+
+        The networks of three and four input images (the reference's `--mode fusion`, trainer.py:74-134) train after
+        `fine_tune(fusion=True)`, on fixed or batch statistics.  The keyword exists because the bare call
+        on such a network was defined, before their training was built, to raise NotImplementedError, and callers and tests
+        rely on that answer -- as `train(True)` keeps raising and batch statistics are asked for by a keyword.  It has no
+        effect on the network of two images."""
+        if mode and self.num_img != 2 and not fusion:
+            raise NotImplementedError("training of the fusion variants (num_img = 3, 4) is not built: PhaseNet.fine_tune needs num_img = 2 "
+                                      "-- or the keyword fusion=True, which trains them")
         self.fine_tuning = bool(mode)
         self.batch_stats = self.fine_tuning and bool(batch_stats)
         for blk in self.layers:
@@ -266,11 +273,16 @@ class PhaseNet(PackedModule):
         channel order [feature | phase | amp | prediction]: fixed-statistics fine-tuning.  Taken only after fine_tune(), with grad
         mode on and a parameter of self.layers requiring grad -- or, after fine_tune(batch_stats=True), by every call (section 17:
         each block takes its batch's statistics; the shared last block takes fresh ones at every level it serves and moves its
-        running statistics once per level, coarse to fine).  The normalised inputs and the maxima get no gradient."""
+        running statistics once per level, coarse to fine).  The normalised inputs and the maxima get no gradient.
+        Three and four input images (after fine_tune(fusion=True), section 20): block 0 sees num_img planes and predicts
+        pred_channels[0], a band level brings 4 * num_img phase and amplitude planes, and the heads are the _n entry points."""
         from . import grad as G
+        n_img = self.num_img
         low_in = vals.low_level.detach().contiguous()
+        if low_in.shape[1] != n_img:
+            raise RuntimeError(f"PhaseNet(num_img={n_img}): the low level has {low_in.shape[1]} images")
         f, c = G.block_forward(self.layers[0], low_in)                                     # :113
-        low = G.blend_low(c, low_in, self.max_low_level)                                   # :115-116 + :96-98
+        low = G.blend_low(c, low_in, self.max_low_level, n_img)                            # :115-121 + :96-98
         hs = vals.high_level.shape
         high = torch.zeros((hs[0], 1, hs[2], hs[3]), dtype=torch.float32, device=low_in.device)   # :127-128
         phases, amps = [], []
@@ -278,9 +290,11 @@ class PhaseNet(PackedModule):
             ph, am = vals.phase[idx].detach(), vals.amplitude[idx].detach()
             i = idx + 1 if idx + 1 < len(self.layers) - 1 else len(self.layers) - 1        # :148
             blk = self.layers[i]
+            if ph.shape[1] != 4 * n_img:
+                raise RuntimeError(f"PhaseNet(num_img={n_img}): level {idx} has {ph.shape[1]} phase planes, expected {4 * n_img}")
             x = G.level_input(f, c, ph, am)                                                # :138-141
             f = G.block_features(blk, x)
-            c, p_out, a_out = G.level_head(blk, f, am, self.max_amplitudes[idx])           # :149-168 + :80-90
+            c, p_out, a_out = G.level_head(blk, f, am, self.max_amplitudes[idx], n_img)    # :149-168 + :80-90
             phases.append(p_out); amps.append(a_out)
         for _ in range(self.pyr.height - 2 - m):                                           # :91-93
             phases.append(0); amps.append(0)

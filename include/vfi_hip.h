@@ -499,6 +499,42 @@ int vfi_phasenet_predict_backward(const float *feat, long long feat_bstride, con
                                   long long gpi_bstride, float *grad_feat, long long gf_bstride, float *grad_weight,
                                   float *grad_bias, float *workspace, int N, int HW, vfi_stream_t stream);
 
+/* The three adjoints above for PhaseNet with num_img = 2, 3 or 4 input images: the adjoints of vfi_phasenet_emit_n,
+ * vfi_phasenet_emit_low_n and vfi_phasenet_predict_n.  Same rules.  For num_img = 2 and 4 each runs the kernel of its two-image
+ * counterpart (the blend reads the first two images only: planes 8..15 of amp_in and 2..3 of low_in are never read, and pred
+ * is not read by the two emit adjoints); any other num_img is VFI_ERR_UNSUPPORTED.  For num_img = 3 pred is an input of all
+ * three, because the second blend's adjoint needs it.
+ *
+ * vfi_phasenet_emit_n_backward, num_img = 3: pred (N,12,HW), amp_in (N,12,HW), grad_pred (N,12,HW).  With b = (pred[4:8]+1)/2,
+ * fb = (pred[8:12]+1)/2 and amp1 = b*amp_in[4:8] + (1-b)*amp_in[0:4]:
+ *   grad_pred[0:4]  = pi * grad_phase
+ *   grad_pred[4:8]  = grad_amp * max_amp[n] * fb * (amp_in[4:8] - amp_in[0:4]) / 2
+ *   grad_pred[8:12] = grad_amp * max_amp[n] * (amp1 - amp_in[8:12]) / 2
+ * Either upstream gradient may be NULL (= zero); pred, amp_in and max_amp are read only with grad_amp. */
+int vfi_phasenet_emit_n_backward(const float *grad_phase, const float *grad_amp, const float *pred, long long pred_bstride,
+                                 const float *amp_in, long long amp_bstride, const float *max_amp, float *grad_pred,
+                                 long long gp_bstride, int N, int HW, int num_img, vfi_stream_t stream);
+
+/* vfi_phasenet_emit_low_n_backward, num_img = 3: pred (N,2,HW), low_in (N,3,HW), grad_pred (N,2,HW).  With a = (pred[0]+1)/2,
+ * fa = (pred[1]+1)/2 and low1 = a*low_in[0] + (1-a)*low_in[1]:
+ *   grad_pred[0] = grad_low * max_low[n] * fa * (low_in[0] - low_in[1]) / 2
+ *   grad_pred[1] = grad_low * max_low[n] * (low1 - low_in[2]) / 2 */
+int vfi_phasenet_emit_low_n_backward(const float *grad_low, const float *pred, long long pred_bstride, const float *low_in,
+                                     long long low_bstride, const float *max_low, float *grad_pred, long long gp_bstride, int N,
+                                     int HW, int num_img, vfi_stream_t stream);
+
+/* vfi_phasenet_predict_n_backward: vfi_phasenet_predict_backward's contract.  num_img = 2 and 4 ARE that entry point (same
+ * launches, VFI_PHASENET_HEAD_WORKSPACE_FLOATS suffice).  num_img = 3: pred, grad_pred_in (N,12,HW), weight (12,64),
+ * grad_weight (12,64), grad_bias (12); g = the emit adjoint above + grad_pred_in, gz = g * (1 - pred^2), grad_feat[k] =
+ * sum_j weight[j][k] gz[j] (written, not accumulated).  Block partials are 12 * 64 + 12 floats:
+ * `workspace` holds VFI_PHASENET_HEAD_N_WORKSPACE_FLOATS. */
+#define VFI_PHASENET_HEAD_N_WORKSPACE_FLOATS (1024 * 780)
+int vfi_phasenet_predict_n_backward(const float *feat, long long feat_bstride, const float *pred, long long pred_bstride,
+                                    const float *amp_in, long long amp_bstride, const float *max_amp, const float *weight,
+                                    const float *grad_phase, const float *grad_amp, const float *grad_pred_in,
+                                    long long gpi_bstride, float *grad_feat, long long gf_bstride, float *grad_weight,
+                                    float *grad_bias, float *workspace, int N, int HW, int num_img, vfi_stream_t stream);
+
 /* Batch-statistics BatchNorm of a block (reference src/phase_net/block.py:17, nn.BatchNorm2d in training mode, with the ELU
  * of block.py:18): per-channel mean[c] and BIASED variance var[c] of y (N, C, HW; batch stride y_bstride) over the samples
  * and pixels.  Two stages: every channel's N * HW values are cut into equal chunks by (N, C, HW) alone, one block writes

@@ -6,7 +6,11 @@ composition of the section-14 entry points.  Per-call HIP events.
 
 --batch-stats: the same step with BatchNorm on the batch's statistics (the forward without a graph is
 then that route under no_grad, running statistics updated), and the three batch-statistics kernels alone at the finest level's
-shape (3 x 64 x 1080 x 1920) with their algorithmic bytes."""
+shape (3 x 64 x 1080 x 1920) with their algorithmic bytes.
+
+--num-img 3 | 4: the same measurements for the pyramid-domain fusion networks: the head adjoint is
+vfi_phasenet_predict_n_backward against the composition over vfi_phasenet_emit_n_backward, the step runs
+PhaseNetCore(num_img).fine_tune(fusion=True) on 3 * num_img images.  The default, 2, prints what it always did."""
 import argparse
 import math
 import os
@@ -16,6 +20,7 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "fusion-method-for-video-frame-interpolation_amd"), os.path.join(ROOT, "tests")]
+import phasenet_fusion_ref as FR  # noqa: E402
 import phasenet_walk_ref as W  # noqa: E402
 from vfi_amd import ops  # noqa: E402
 from vfi_amd.phase_net import grad as G  # noqa: E402
@@ -53,6 +58,23 @@ def head(h, w, n=3, iters=10, warm=3):
           f"five-launch composition {t_old:.3f} ms, ratio {t_old / t_new:.2f}")
 
 
+def head_n(h, w, num_img, n=3, iters=10, warm=3):
+    """head() for three and four input images, on the walk's own layouts: [feature | pred] and the whole amplitude block."""
+    dev = torch.device("cuda:0")
+    g = torch.Generator().manual_seed(0)
+    r = lambda *s: torch.randn(s, generator=g).to(dev)
+    pb = FR.pred_channels(num_img)[1]
+    fp = r(n, 64 + pb, h, w)
+    fp[:, 64:] = torch.tanh(fp[:, 64:])
+    f, pred, amp, mx, wp = fp[:, :64], fp[:, 64:], torch.rand((n, 4 * num_img, h, w), generator=g).to(dev), torch.ones(n, device=dev), r(pb, 64, 1, 1) / 8
+    gp, ga, gc = r(n * 4, 1, h, w), r(n * 4, 1, h, w), r(n, pb, h, w)
+    t_new = timed(lambda: ops.phasenet_predict_n_backward(f, pred, amp, mx, wp, num_img, gp, ga, gc), iters, warm)
+    t_old = timed(lambda: G.head_backward_composed(f, pred, amp, mx, wp, gp, ga, gc, num_img=num_img), iters, warm)
+    planes = 64 + pb + pb + 4 + (20 if num_img == 3 else 12) + 64
+    print(f"head adjoint, num_img={num_img} N={n} {h}x{w}: one pass {t_new:.3f} ms ({4e-9 * n * h * w * planes / (t_new * 1e-3):.0f} GB/s of {planes} planes), "
+          f"composition {t_old:.3f} ms, ratio {t_old / t_new:.2f}")
+
+
 def bn_kernels(h, w, n=3, c=64, iters=10, warm=3):
     dev = torch.device("cuda:0")
     g = torch.Generator().manual_seed(0)
@@ -72,14 +94,19 @@ def bn_kernels(h, w, n=3, c=64, iters=10, warm=3):
         print(f"  {name:40s} {ms:7.3f} ms  {passes * planes / (ms * 1e-3):6.0f} GB/s of {passes} tensor passes")
 
 
-def step(h, w, m, n=3, iters=3, warm=1, batch_stats=False):
+def step(h, w, m, n=3, iters=3, warm=1, batch_stats=False, num_img=2):
     dev = torch.device("cuda:0")
     height = calc_pyr_height(torch.empty(1, h, w))
-    core = PhaseNetCore(height, dev).fine_tune(batch_stats=batch_stats)
-    core.load_state_dict(W.net_state(0))
     pyr = Pyramid(height=height, nbands=4, scale_factor=W.S2, device=dev)
-    imgs = torch.rand((2 * n, h, w), generator=torch.Generator().manual_seed(1)).to(dev)
-    vals, bufs = pyr.filter(imgs, concat_frames=2, phase_scale=1.0 / math.pi)
+    imgs = torch.rand((num_img * n, h, w), generator=torch.Generator().manual_seed(1)).to(dev)
+    if num_img == 2:
+        core = PhaseNetCore(height, dev).fine_tune(batch_stats=batch_stats)
+        core.load_state_dict(W.net_state(0))
+        vals, bufs = pyr.filter(imgs, concat_frames=2, phase_scale=1.0 / math.pi)
+    else:
+        core = PhaseNetCore(height, dev, num_img=num_img).fine_tune(batch_stats=batch_stats, fusion=True)
+        core.load_state_dict(FR.net_state(0, num_img))
+        vals, bufs = pyr.filter(imgs, concat_frames=num_img, phase_scale=1.0 / math.pi, pred_channels=core.pred_channels)
     nv = core.normalize_vals(vals, concat=bufs)
     with torch.no_grad():
         t_inf = timed(lambda: core(nv, m), iters, warm)
@@ -104,7 +131,7 @@ def step(h, w, m, n=3, iters=3, warm=1, batch_stats=False):
     t_step = timed(full, iters, warm)
     t_bwd = t_step - t_fwd
     print(f"PhaseNet walk, N={n} {h}x{w}, height {height}, m = {m if m is not None else height - 2}" +
-          (", batch statistics" if batch_stats else ""))
+          (", batch statistics" if batch_stats else "") + (f", num_img = {num_img}" if num_img != 2 else ""))
     print(f"  {'forward without a graph' if batch_stats else 'inference forward'      :26s} {t_inf:8.3f} ms")
     print(f"  forward as a graph + loss  {t_fwd:8.3f} ms")
     print(f"  backward                   {t_bwd:8.3f} ms = {t_bwd / t_inf:.2f} x that forward")
@@ -113,14 +140,17 @@ def step(h, w, m, n=3, iters=3, warm=1, batch_stats=False):
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("--batch-stats", action="store_true", help="BatchNorm on batch statistics (DESIGN.md section 17)")
+    ap.add_argument("--num-img", type=int, choices=(2, 3, 4), default=2, help="input images of the network (DESIGN.md section 20)")
     args = ap.parse_args()
     if args.batch_stats:
         bn_kernels(1080, 1920)
-    else:
+    elif args.num_img == 2:
         head(1080, 1920)
+    else:
+        head_n(1080, 1920, args.num_img)
     torch.cuda.empty_cache()
     for m in (None, 4):
-        step(1080, 1920, m, batch_stats=args.batch_stats)
+        step(1080, 1920, m, batch_stats=args.batch_stats, num_img=args.num_img)
         torch.cuda.empty_cache()
 
 
