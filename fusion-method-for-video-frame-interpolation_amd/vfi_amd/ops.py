@@ -228,6 +228,31 @@ def resize_bilinear(x, size, align_corners, relu_input=False, residual=None, out
     return out
 
 
+# PhaseNet.forward takes vfi_phasenet_level_tail from this many pixels per plane on.  A tile of the one-pass kernel walks its 64
+# channels in 18 dependent stages, about 45 us however small the level; the two launches it replaces need that long at
+# 135 x 240 and are quicker below (profiles/r06_phasenet_tail.txt).
+PHASENET_TAIL_MIN_PIXELS = 40000
+
+
+def phasenet_level_tail(fp, cp, amp_in, max_amp, x_next):
+    """A two-image band level's head and the next level's resize in one vfi_phasenet_level_tail call: fp[:, :64] the block's
+    features, cp the packed 64 -> 8 prediction map, amp_in the level's 8 normalised amplitude planes, x_next the first 72
+    channels of the next level's block input (a channel slice), which receive bilinear_resize([feature | prediction],
+    align_corners=False).  -> (phase_out, amp_out), each (4 N, 1, h, w)."""
+    n, _, h, w = fp.shape
+    if cp.cin != 64 or cp.cout != 8 or cp.ks != 1 or fp.shape[1] < 64 or x_next.shape[:2] != (n, 72) or amp_in.shape != (n, 8, h, w):
+        raise VfiLibraryError("phasenet_level_tail: shape mismatch")
+    ho, wo = x_next.shape[2:]
+    fpp, fps = _slice_ptr(fp[:, :64], "fp")
+    ap, as_ = _slice_ptr(amp_in, "amp_in")
+    xp, xs = _slice_ptr(x_next, "x_next")
+    p_out, a_out = new((n * 4, 1, h, w), fp), new((n * 4, 1, h, w), fp)
+    work = ("byte", 4.0 * n * ((64 + 8 + 8) * h * w + 72 * ho * wo), "phasenet_level_tail_kernel") if _lib.PROFILE is not None else None
+    _lib.call("vfi_phasenet_level_tail", fpp, fps, cp.packed.data_ptr(), cp.bias.data_ptr(), ap, as_, _lib.dptr(max_amp, "max_amp"), xp, xs,
+              p_out.data_ptr(), a_out.data_ptr(), n, h, w, ho, wo, _lib.stream_ptr(), work=work)
+    return p_out, a_out
+
+
 def softmax_channels_(x):
     n, c, h, w = x.shape
     xp, xs = _slice_ptr(x, "x")

@@ -10,7 +10,9 @@ Execution on the MI355X (all arithmetic in libvfi_hip.so):
     (the first conv's input channels are permuted to match at pack time); the previous block writes
     feature and prediction into ONE tensor, so a single bilinear-resize launch fills the first 64+P
     channels, and normalize_vals writes phase/pi and amp/max straight into the last 16;
-  * the per-level blend + de-normalisation (phase_net.py:155-168, :80-105) is one launch per level.
+  * the per-level blend + de-normalisation (phase_net.py:155-168, :80-105) is one launch per level: the prediction map's
+    launch -- and, below a level whose first conv is 3x3, also the launch that resizes into that level's buffer
+    (vfi_phasenet_level_tail, two images only).
 Maxima are returned/kept per call on the module (as the reference does, phase_net.py:53,59,70).
 
 `num_img` = 3 and 4 are the reference's pyramid-domain fusion networks (phase_net.py:21-35, 119-121, 158-162; DESIGN.md section
@@ -23,6 +25,7 @@ section 16).  After `fine_tune(batch_stats=True)` every forward takes that route
 and the running statistics updated (training from scratch, section 17).  Every other call runs the code above, unchanged.
 """
 import math
+import os
 
 import torch
 
@@ -232,28 +235,51 @@ class PhaseNet(PackedModule):
         high = torch.zeros((hs[0], 1, hs[2], hs[3]), dtype=torch.float32, device=low_in.device)   # :127-128
 
         concat = getattr(vals, "concat", None)
-        phases, amps = [], []
-        for idx in range(m):
-            p_prev = fp.shape[1] - 64
+
+        def level_input(idx):
+            if concat is not None:
+                return concat[idx]
+            # values not produced by normalize_vals: fill the block input buffer here
             ph, am = vals.phase[idx], vals.amplitude[idx]
             _, c, h, w = ph.shape
-            if concat is not None:
-                x = concat[idx]
-            else:  # values not produced by normalize_vals: fill the block input buffer here
-                x = ops.new((b, 64 + p_prev + 2 * c, h, w), low_in)
-                ops.affine_slice(ph.contiguous(), x[:, 64 + p_prev:64 + p_prev + c])
-                ops.affine_slice(am.contiguous(), x[:, 64 + p_prev + c:])
-            i = idx + 1 if idx + 1 < len(self.layers) - 1 else len(self.layers) - 1        # :148
+            p_prev = p_low if idx == 0 else p_band
+            x = ops.new((b, 64 + p_prev + 2 * c, h, w), low_in)
+            ops.affine_slice(ph.contiguous(), x[:, 64 + p_prev:64 + p_prev + c])
+            ops.affine_slice(am.contiguous(), x[:, 64 + p_prev + c:])
+            return x
+
+        def layer(idx):
+            return idx + 1 if idx + 1 < len(self.layers) - 1 else len(self.layers) - 1     # :148
+
+        # two images, and the next level's first conv is the 3x3 that reads a materialised resize: this level's head and that
+        # resize are one launch (vfi_phasenet_level_tail) from ops.PHASENET_TAIL_MIN_PIXELS pixels on.  VFI_PHASENET_TAIL, read
+        # per call, is an A/B aid: 0 restores the two launches everywhere, 1 takes the one launch at every size
+        tail_env = os.environ.get("VFI_PHASENET_TAIL", "")
+        tail_on = n_img == 2 and not ops.FUSED_RESIZE and tail_env != "0"
+        tail_min = 0 if tail_env == "1" else ops.PHASENET_TAIL_MIN_PIXELS
+        phases, amps = [], []
+        x_next = None
+        for idx in range(m):
+            p_prev = p_low if idx == 0 else p_band
+            _, c, h, w = vals.phase[idx].shape
+            filled = x_next is not None      # the level below has already written [feature | prediction], resized, into x
+            x = x_next if filled else level_input(idx)
+            i = layer(idx)
             fused = packed[i][0].ks == 3 and (64 + p_prev) % 8 == 0
-            if not fused:
+            if not fused and not filled:
                 ops.resize_bilinear(fp, (h, w), align_corners=False, out=x[:, :64 + p_prev])   # :138-141
-            fp = block(i, x, ops.new((b, 64 + p_band, h, w), low_in), prev=fp if fused else None, head=False)
+            tail = tail_on and idx + 1 < m and h * w >= tail_min and packed[layer(idx + 1)][0].ks == 3 and (64 + p_band) % 8 == 0
+            fp = block(i, x, ops.new((b, 64 if tail else 64 + p_band, h, w), low_in), prev=fp if fused and not filled else None, head=False)
             amp_in = x[:, 64 + p_prev + c:]
             # prediction map (1x1, tanh) + this level's outputs in one pass over the 64 feature channels (:149-168)
             cp = packed[i][2]
             if cp.cout != p_band or cp.ks != 1:
                 raise RuntimeError(f"PhaseNet: a band level's prediction map must be a 1x1 layer with {p_band} outputs (phase_net.py:23-35)")
-            if n_img == 2:
+            x_next = None
+            if tail:                 # ... and the resize of (feature | prediction) into the next level's input, same pass
+                x_next = level_input(idx + 1)
+                p_out, a_out = ops.phasenet_level_tail(fp, cp, amp_in, self.max_amplitudes[idx], x_next[:, :64 + p_band])
+            elif n_img == 2:
                 p_out, a_out = ops.new((b * 4, 1, h, w), low_in), ops.new((b * 4, 1, h, w), low_in)
                 _lib.call("vfi_phasenet_predict", fp.data_ptr(), fp.stride(0), cp.packed.data_ptr(), cp.bias.data_ptr(), amp_in.data_ptr(),
                           x.stride(0), self.max_amplitudes[idx].data_ptr(), fp[:, 64:].data_ptr(), fp.stride(0), p_out.data_ptr(),

@@ -280,6 +280,18 @@ int vfi_phasenet_predict(const float *feat, long long feat_bstride, const float 
                          const float *amp_in, long long amp_bstride, const float *max_amp, float *pred, long long pred_bstride,
                          float *phase_out, float *amp_out, int N, int Cin, int H, int W, vfi_stream_t stream);
 
+/* A band level's head and the next level's resize in one pass (phase_net.py:138-168): vfi_phasenet_predict's phase_out and
+ * amp_out from feat (N,64,H*W), and x_next[:, 0:72] (a channel slice of the next level's block input, N x (>= 72) x Hout x Wout
+ * with its batch stride) = bilinear resize, align_corners=False, of [feat 64 | pred 8].  The un-resized pred is not an output.
+ * phase_out and amp_out have the bits of vfi_phasenet_predict.  One kernel where vfi_phasenet_predict streams and the target is
+ * no smaller than the source: its resized planes evaluate vfi_resize_bilinear's expression and may differ from it in the last
+ * bit (fused multiply-adds chosen by the compiler).  Else vfi_phasenet_predict and vfi_resize_bilinear themselves (pred then
+ * passes through the head of x_next, so 8*H*W <= 64*Hout*Wout is required). */
+int vfi_phasenet_level_tail(const float *feat, long long feat_bstride, const float *packed_w, const float *bias,
+                            const float *amp_in, long long amp_bstride, const float *max_amp, float *x_next,
+                            long long next_bstride, float *phase_out, float *amp_out, int N, int H, int W, int Hout, int Wout,
+                            vfi_stream_t stream);
+
 /* phase_net.py:113-116 + :96-98: low_out (N,HW) = (a*low_in[:,0] + (1-a)*low_in[:,1])*max_low[n], a = (pred+1)/2. */
 int vfi_phasenet_emit_low(const float *pred, long long pred_bstride, const float *low_in, long long low_bstride,
                           const float *max_low, float *low_out, int N, int HW, vfi_stream_t stream);
