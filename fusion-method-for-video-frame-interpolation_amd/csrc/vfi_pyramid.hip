@@ -672,12 +672,21 @@ int fft2d_c2r(const vfi_pyr_plan *p, float2 *half, float *out, int N, hipStream_
     return pass_rows(p->frame, half, out, (long long)N * p->H, wh, p->W, vfi::fft::kLoadHalf, vfi::fft::kStoreReal, true, s);
 }
 
-PlaneMap make_map(const int *plane_index, int level, int N, int nb, int flags) {
+// One slice of a call: images [first, first + n) of the call's `total`.  A call of more than the plan's max_images images
+// runs as consecutive slices on the plan's one workspace; every slice's map addresses the caller's tensors of the WHOLE
+// call (a band-major tensor's bands lie `total` planes apart, and a caller's plane_index has `total` entries per level).
+struct Slice {
+    int first, n, total;
+};
+
+PlaneMap make_map(const int *plane_index, int level, const Slice &sl, int nb, int flags) {
     PlaneMap pm;
     const bool band_major = flags & VFI_PYR_BAND_MAJOR;
-    for (int d = 0; d < kMaxImages; ++d)
-        pm.idx[d] = d < N ? (plane_index ? plane_index[level * N + d] : (band_major ? d : d * nb)) : 0;
-    pm.band_stride = band_major ? N : 1;
+    for (int d = 0; d < kMaxImages; ++d) {
+        const int g = sl.first + d;
+        pm.idx[d] = d < sl.n ? (plane_index ? plane_index[(size_t)level * sl.total + g] : (band_major ? g : g * nb)) : 0;
+    }
+    pm.band_stride = band_major ? sl.total : 1;
     pm.complex_coeff = (flags & VFI_PYR_COMPLEX_COEFF) ? 1 : 0;
     return pm;
 }
@@ -718,6 +727,7 @@ struct AnalyzeCall {
     float eps = 0.0f;
     bool adjoint = false;
     const float *const *fphase = nullptr, *const *famp = nullptr;   // forward inputs per level (unused with VFI_PYR_COMPLEX_COEFF)
+    Slice slice = {0, 0, 0};       // set by pyr_analyze_impl's walk; high / low already point at the slice's first image
     bool grad() const { return adjoint && !(flags & VFI_PYR_COMPLEX_COEFF); }      // gradient epilogue on (phase, amplitude)
 };
 
@@ -728,7 +738,7 @@ LevelColsArgs ana_cols_args(const vfi_pyr_plan *p, int k, const AnalyzeCall &c, 
 RowsPolarGradArgs ana_rows_args(const vfi_pyr_plan *p, int k, int N, const AnalyzeCall &c, float2 *T) {
     const Level &L = p->lev[k];
     const long long rows = (long long)N * p->nbands * L.h;
-    return RowsPolarGradArgs{{L.pw, T, c.phase[k], c.amp ? c.amp[k] : nullptr, make_map(c.plane_index, k, N, p->nbands, c.flags), rows, L.h,
+    return RowsPolarGradArgs{{L.pw, T, c.phase[k], c.amp ? c.amp[k] : nullptr, make_map(c.plane_index, k, c.slice, p->nbands, c.flags), rows, L.h,
                               level_row_lines(L.pw, rows),
                               c.adjoint ? 1.0f / ((float)p->H * (float)p->W) : 1.0f / ((float)L.h * (float)L.w), c.phase_scale,
                               c.amp_max ? p->amp_bits + (size_t)k * c.groups : nullptr, c.groups},
@@ -820,21 +830,9 @@ int ana_rows(const vfi_pyr_plan *p, int k, int N, const AnalyzeCall &c, hipStrea
     return c.grad() ? vfi::pyrw::launch_rows_polar_grad(vfi::pyrw::RowsGradArgs{ra, g.fphase, g.famp}, s) : vfi::pyrw::launch_rows_polar(ra, s);
 }
 
-int pyr_analyze_impl(const vfi_pyr_plan *p, const float *img, int N, const AnalyzeCall &c, vfi_stream_t stream) {
-    VFI_REQUIRE(p && img, VFI_ERR_INVALID_ARG, "vfi_pyr_analyze: null pointer");
-    VFI_REQUIRE(!c.amp_max || (c.groups >= 1 && c.groups <= 4 && !(c.flags & VFI_PYR_COMPLEX_COEFF)), VFI_ERR_INVALID_ARG,
-                "vfi_pyr_analyze_max: groups must be 1..4 and the outputs (phase, amplitude)");
-    VFI_REQUIRE(N >= 1 && N <= p->max_images, VFI_ERR_INVALID_ARG, "vfi_pyr_analyze: N=%d (plan max %d)", N, p->max_images);
-    VFI_REQUIRE((c.phase && (c.amp || (c.flags & VFI_PYR_COMPLEX_COEFF))) || c.level_mask == 0, VFI_ERR_INVALID_ARG,
-                "vfi_pyr_analyze: null phase/amp tables");
-    for (int k = 0; k < p->nlev; ++k) {
-        if (!((c.level_mask >> k) & 1ull)) continue;
-        VFI_REQUIRE(c.phase[k] && ((c.flags & VFI_PYR_COMPLEX_COEFF) || c.amp[k]), VFI_ERR_INVALID_ARG,
-                    "vfi_pyr_analyze: null output for level %d", k);
-        VFI_REQUIRE(!c.grad() || (c.fphase[k] && c.famp[k]), VFI_ERR_INVALID_ARG, "vfi_pyr_synthesize_backward: null input for level %d", k);
-    }
-    hipStream_t s = vfi::as_stream(stream);
-    const int H = p->H, W = p->W;
+// the analysis passes of one slice (c.slice; N = c.slice.n images from img on)
+int analyze_slice(const vfi_pyr_plan *p, const float *img, const AnalyzeCall &c, hipStream_t s) {
+    const int N = c.slice.n, H = p->H, W = p->W;
     const float inv_full = 1.0f / ((float)H * (float)W);
     int rc;
     if (c.amp_max && hipMemsetAsync(p->amp_bits, 0, sizeof(unsigned) * p->nlev * c.groups, s) != hipSuccess)
@@ -864,6 +862,34 @@ int pyr_analyze_impl(const vfi_pyr_plan *p, const float *img, int N, const Analy
         const int count = p->nlev * c.groups;
         hipLaunchKernelGGL(pyr_amp_max_finish_kernel, dim3(ceil_div(count, 64)), dim3(64), 0, s, p->amp_bits, c.amp_max, count, c.eps);
     }
+    return VFI_OK;
+}
+
+// Any N >= 1: consecutive slices of at most max_images images, the last one shorter, each through analyze_slice on the
+// plan's workspace and the caller's stream (stream order keeps a slice off the workspace until the one before is done).
+// The amplitude maxima of vfi_pyr_analyze_max are reduced inside one launch, so that form stays within one slice.
+int pyr_analyze_impl(const vfi_pyr_plan *p, const float *img, int N, const AnalyzeCall &c, vfi_stream_t stream) {
+    VFI_REQUIRE(p && img, VFI_ERR_INVALID_ARG, "vfi_pyr_analyze: null pointer");
+    VFI_REQUIRE(!c.amp_max || (c.groups >= 1 && c.groups <= 4 && !(c.flags & VFI_PYR_COMPLEX_COEFF)), VFI_ERR_INVALID_ARG,
+                "vfi_pyr_analyze_max: groups must be 1..4 and the outputs (phase, amplitude)");
+    VFI_REQUIRE(N >= 1 && (!c.amp_max || N <= p->max_images), VFI_ERR_INVALID_ARG, "vfi_pyr_analyze: N=%d (plan max %d)", N, p->max_images);
+    VFI_REQUIRE((c.phase && (c.amp || (c.flags & VFI_PYR_COMPLEX_COEFF))) || c.level_mask == 0, VFI_ERR_INVALID_ARG,
+                "vfi_pyr_analyze: null phase/amp tables");
+    for (int k = 0; k < p->nlev; ++k) {
+        if (!((c.level_mask >> k) & 1ull)) continue;
+        VFI_REQUIRE(c.phase[k] && ((c.flags & VFI_PYR_COMPLEX_COEFF) || c.amp[k]), VFI_ERR_INVALID_ARG,
+                    "vfi_pyr_analyze: null output for level %d", k);
+        VFI_REQUIRE(!c.grad() || (c.fphase[k] && c.famp[k]), VFI_ERR_INVALID_ARG, "vfi_pyr_synthesize_backward: null input for level %d", k);
+    }
+    hipStream_t s = vfi::as_stream(stream);
+    const size_t full = (size_t)p->H * p->W, lowpx = (size_t)p->low.h * p->low.w;
+    for (int first = 0; first < N; first += p->max_images) {
+        AnalyzeCall sc = c;
+        sc.slice = Slice{first, std::min(p->max_images, N - first), N};
+        if (c.high) sc.high = c.high + first * full;
+        if (c.low) sc.low = c.low + first * lowpx;
+        if (const int rc = analyze_slice(p, img + first * full, sc, s)) return rc;
+    }
     return vfi::check_launch("vfi_pyr_analyze");
 }
 
@@ -888,6 +914,7 @@ struct SynthCall {
     bool adjoint = false;
     const float *const *fphase = nullptr, *const *famp = nullptr;   // the forward's outputs per level (unused with VFI_PYR_COMPLEX_COEFF)
     float phase_scale = 1.0f;
+    Slice slice = {0, 0, 0};       // set by pyr_synthesize_impl's walk; high / low already point at the slice's first image
     bool grad() const { return adjoint && !(flags & VFI_PYR_COMPLEX_COEFF); }      // gradient prologue on (d phase, d amplitude)
 };
 
@@ -896,7 +923,7 @@ int syn_rows(const vfi_pyr_plan *p, int k, int N, const SynthCall &c, hipStream_
     const long long rows = (long long)N * p->nbands * L.h;
     const bool grad = c.grad();
     const RowsPolarGradArgs g{{L.pw, p->bands, const_cast<float *>(c.phase[k]), const_cast<float *>(c.amp ? c.amp[k] : nullptr),
-                               make_map(c.plane_index, k, N, p->nbands, c.flags), rows, L.h, level_row_lines(L.pw, rows),
+                               make_map(c.plane_index, k, c.slice, p->nbands, c.flags), rows, L.h, level_row_lines(L.pw, rows),
                                grad ? 1.0f / c.phase_scale : 1.0f, grad ? c.phase_scale : 1.0f, nullptr, 1},
                               grad ? c.fphase[k] : nullptr, grad ? c.famp[k] : nullptr};
     if (L.wave[kWaveRows].M) {
@@ -922,12 +949,9 @@ int syn_cols(const vfi_pyr_plan *p, int k, int N, const float *P, const float2 *
                                                                                               cols_lds(L), s, ca);
 }
 
-int pyr_synthesize_impl(const vfi_pyr_plan *p, const SynthCall &c, float *img, int N, const char *who, vfi_stream_t stream) {
-    VFI_REQUIRE(N >= 1 && N <= p->max_images, VFI_ERR_INVALID_ARG, "%s: N=%d (plan max %d)", who, N, p->max_images);
-    VFI_REQUIRE((c.phase && (c.amp || (c.flags & VFI_PYR_COMPLEX_COEFF))) || c.level_mask == 0, VFI_ERR_INVALID_ARG,
-                "%s: null phase/amp tables", who);
-    hipStream_t s = vfi::as_stream(stream);
-    const int H = p->H, W = p->W;
+// the synthesis passes of one slice (c.slice; N = c.slice.n images written from img on)
+int synthesize_slice(const vfi_pyr_plan *p, const SynthCall &c, float *img, const char *who, hipStream_t s) {
+    const int N = c.slice.n, H = p->H, W = p->W;
     int rc;
     // coarsest: res = FFT(low) (zeros when low is NULL); the adjoint's low residual carries 1 / (hL wL) where the final has 1 / (H W)
     float2 *res = p->lod[p->nlev & 1];
@@ -959,6 +983,23 @@ int pyr_synthesize_impl(const vfi_pyr_plan *p, const SynthCall &c, float *img, i
     if ((rc = fft2d_c2c(p->frame, res, N, true, s))) return rc;
     const long long tot = (long long)N * H * W;
     hipLaunchKernelGGL(complex_real_kernel, dim3(blocks_1d(tot)), dim3(256), 0, s, res, img, tot, 1.0f / ((float)H * (float)W));
+    return VFI_OK;
+}
+
+// any N >= 1, in slices as pyr_analyze_impl
+int pyr_synthesize_impl(const vfi_pyr_plan *p, const SynthCall &c, float *img, int N, const char *who, vfi_stream_t stream) {
+    VFI_REQUIRE(N >= 1, VFI_ERR_INVALID_ARG, "%s: N=%d", who, N);
+    VFI_REQUIRE((c.phase && (c.amp || (c.flags & VFI_PYR_COMPLEX_COEFF))) || c.level_mask == 0, VFI_ERR_INVALID_ARG,
+                "%s: null phase/amp tables", who);
+    hipStream_t s = vfi::as_stream(stream);
+    const size_t full = (size_t)p->H * p->W, lowpx = (size_t)p->low.h * p->low.w;
+    for (int first = 0; first < N; first += p->max_images) {
+        SynthCall sc = c;
+        sc.slice = Slice{first, std::min(p->max_images, N - first), N};
+        if (c.high) sc.high = c.high + first * full;
+        if (c.low) sc.low = c.low + first * lowpx;
+        if (const int rc = synthesize_slice(p, sc, img + first * full, who, s)) return rc;
+    }
     return vfi::check_launch(who);
 }
 
@@ -967,13 +1008,17 @@ int pyr_synthesize_impl(const vfi_pyr_plan *p, const SynthCall &c, float *img, i
 extern "C" int vfi_pyr_apply_filter(vfi_pyr_plan *p, int filter_id, const float *img, int N, float *out, vfi_stream_t stream) {
     VFI_REQUIRE(p && img && out, VFI_ERR_INVALID_ARG, "vfi_pyr_apply_filter: null pointer");
     VFI_REQUIRE(filter_id >= 0 && filter_id < (int)p->filters.size(), VFI_ERR_INVALID_ARG, "vfi_pyr_apply_filter: bad filter id %d", filter_id);
-    VFI_REQUIRE(N >= 1 && N <= p->max_images, VFI_ERR_INVALID_ARG, "vfi_pyr_apply_filter: N=%d (plan max %d)", N, p->max_images);
+    VFI_REQUIRE(N >= 1, VFI_ERR_INVALID_ARG, "vfi_pyr_apply_filter: N=%d", N);
     hipStream_t s = vfi::as_stream(stream);
-    int rc;
-    if ((rc = fft2d_r2c(p, img, p->half0, N, s))) return rc;
     const long long per = (long long)p->H * (p->W / 2 + 1);
-    hipLaunchKernelGGL(pyr_gain_kernel, dim3(blocks_1d(per * N)), dim3(256), 0, s, p->half0, p->filters[filter_id], N, per);
-    if ((rc = fft2d_c2r(p, p->half0, out, N, s))) return rc;
+    const size_t full = (size_t)p->H * p->W;
+    for (int first = 0; first < N; first += p->max_images) {      // slices of max_images images (pyr_analyze_impl)
+        const int n = std::min(p->max_images, N - first);
+        int rc;
+        if ((rc = fft2d_r2c(p, img + first * full, p->half0, n, s))) return rc;
+        hipLaunchKernelGGL(pyr_gain_kernel, dim3(blocks_1d(per * n)), dim3(256), 0, s, p->half0, p->filters[filter_id], n, per);
+        if ((rc = fft2d_c2r(p, p->half0, out + first * full, n, s))) return rc;
+    }
     return vfi::check_launch("vfi_pyr_apply_filter");
 }
 
@@ -983,15 +1028,20 @@ extern "C" int vfi_pyr_apply_filter_pair(vfi_pyr_plan *p, int filter_a, const fl
     const int nf = (int)p->filters.size();
     VFI_REQUIRE(filter_a >= 0 && filter_a < nf && filter_b >= 0 && filter_b < nf, VFI_ERR_INVALID_ARG,
                 "vfi_pyr_apply_filter_pair: bad filter ids %d, %d", filter_a, filter_b);
-    VFI_REQUIRE(N >= 1 && 2 * N <= p->max_images, VFI_ERR_INVALID_ARG, "vfi_pyr_apply_filter_pair: N=%d (plan max %d images in all)",
+    VFI_REQUIRE(N >= 1 && p->max_images >= 2, VFI_ERR_INVALID_ARG, "vfi_pyr_apply_filter_pair: N=%d (plan max %d images in all)",
                 N, p->max_images);
     hipStream_t s = vfi::as_stream(stream);
-    int rc;
-    if ((rc = fft2d_r2c(p, img_a, p->half0, N, s)) || (rc = fft2d_r2c(p, img_b, p->half_hi, N, s))) return rc;
     const long long per = (long long)p->H * (p->W / 2 + 1);
-    hipLaunchKernelGGL(pyr_gain_pair_kernel, dim3(blocks_1d(per * N)), dim3(256), 0, s, p->half0, p->half_hi, p->filters[filter_a],
-                       p->filters[filter_b], N, per);
-    if ((rc = fft2d_c2r(p, p->half0, out, N, s))) return rc;
+    const size_t full = (size_t)p->H * p->W;
+    const int cap = p->max_images / 2;      // a slice holds this many images of EACH set
+    for (int first = 0; first < N; first += cap) {
+        const int n = std::min(cap, N - first);
+        int rc;
+        if ((rc = fft2d_r2c(p, img_a + first * full, p->half0, n, s)) || (rc = fft2d_r2c(p, img_b + first * full, p->half_hi, n, s))) return rc;
+        hipLaunchKernelGGL(pyr_gain_pair_kernel, dim3(blocks_1d(per * n)), dim3(256), 0, s, p->half0, p->half_hi, p->filters[filter_a],
+                           p->filters[filter_b], n, per);
+        if ((rc = fft2d_c2r(p, p->half0, out + first * full, n, s))) return rc;
+    }
     return vfi::check_launch("vfi_pyr_apply_filter_pair");
 }
 

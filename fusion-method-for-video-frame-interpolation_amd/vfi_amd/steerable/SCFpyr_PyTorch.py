@@ -4,7 +4,8 @@ src/train/pyramid.py:28-33 and calls at :37,44.  Coefficient layout as the refer
 coeff = [hi (N,H,W), [nbands x (N,h,w,2)] per level finest first, lo (N,hL,wL)] (pyramid.py:56-61).
 
 Backed by one plan per (H, W) in libvfi_hip.so (level geometry, mask tables, the tables of the hand-written FFT
-engines -- no FFT library is linked --, workspace).
+engines -- no FFT library is linked --, workspace).  N is not limited: a plan's workspace holds at most 16 images, and the
+library walks a call of more images in slices of that many, so a whole training batch is one call.
 
 `reconstruct` (and `vfi_amd.train.Pyramid.inv_filter`) is differentiable with respect to its inputs: when grad mode is on
 and an input requires grad it runs as the autograd node `Synthesis`, whose backward is vfi_pyr_synthesize_backward.
@@ -313,10 +314,14 @@ class SCFpyr_PyTorch(object):
         self._plans = {}
 
     def plan(self, h, w, n):
+        """The cached plan of (h, w) for calls of n images.  A plan's max_images (16 at most) is the number of images one
+        slice of a call holds: the library walks a longer call in slices, so the plan is rebuilt only when
+        min(max(n, 6), 16) grows."""
         key = (h, w)
+        want = min(max(n, 6), 16)
         p = self._plans.get(key)
-        if p is None or p.max_images < n:
-            p = Plan(h, w, self.height, self.nbands, self.scale_factor, max(n, 6), self.device)
+        if p is None or p.max_images < want:
+            p = Plan(h, w, self.height, self.nbands, self.scale_factor, want, self.device)
             self._plans[key] = p
         return p
 

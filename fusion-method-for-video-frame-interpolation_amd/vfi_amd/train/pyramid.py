@@ -61,7 +61,8 @@ class Pyramid:
         are (C, F*nbands, h, w) views (channels [f0 b0..b3, f1 b0..b3]) of block-input buffers, lists ordered
         COARSEST first, high (C,F,H,W), low (C,F,hL,wL); see PhaseNet.normalize_vals.  The buffers are [feature 64 | prediction
         P | phase F*nbands | amp F*nbands]; pred_channels=(P of the coarsest level, P of the others), default (1, 8), is
-        PhaseNet(num_img=F).pred_channels.  N = F*C is at most 16 images (the plan's limit).
+        PhaseNet(num_img=F).pred_channels.  N = F*C is at most 16 images here (one slice of the plan: the amplitude maxima
+        are reduced inside one launch); the per-image layout, inv_filter, band_filter and band_filter_pair take any N.
 
         The per-image layout is differentiable with respect to img (autograd node `Analysis`; the gradient of the phase is
         dropped where the amplitude is exactly 0, where torch.atan2 would give NaN).  The concat_frames layout is not:

@@ -596,7 +596,15 @@ int vfi_l1_backward(const float *a, const float *b, const float *upstream, float
  * per-frame construction of `SCFpyr_PyTorch(height, nbands, scale_factor, device)` (reference
  * src/train/pyramid.py:28-33, rebuilt for every frame at src/fusion_net/interpolate_twoframe.py:124-129).  Creation
  * allocates device memory and synchronises; everything else only enqueues.  A plan's workspace belongs to one stream
- * at a time: frames in flight use one plan each. */
+ * at a time: frames in flight use one plan each.
+ * max_images (1..16) sizes the workspace: it is the number of images ONE SLICE of a call holds, not a limit on N.
+ * vfi_pyr_analyze, vfi_pyr_synthesize, their two backward calls and vfi_pyr_apply_filter take any N >= 1 and process
+ * consecutive slices of max_images images (the last one shorter; vfi_pyr_apply_filter_pair: max_images / 2 images of each
+ * set), each through the same passes on the one workspace, in stream order: nothing is allocated, synchronised or copied,
+ * and a call of N <= max_images is one slice.  Every slice addresses the caller's tensors of the whole call: with
+ * VFI_PYR_BAND_MAJOR the bands lie N planes apart, and a plane_index table has N entries per level.
+ * vfi_pyr_analyze_max reduces its maxima inside one launch and keeps N <= max_images; vfi_pyr_plan_multi_levels answers
+ * for one slice (N <= max_images). */
 typedef struct vfi_pyr_plan vfi_pyr_plan;
 
 enum {
@@ -644,7 +652,7 @@ int vfi_pyr_plan_prepare_filter(vfi_pyr_plan *plan, unsigned long long level_mas
                                 int *filter_id);
 int vfi_pyr_apply_filter(vfi_pyr_plan *plan, int filter_id, const float *img, int N, float *out, vfi_stream_t stream);
 /* out = real(ifft2(fft2(img_a) * G_a + fft2(img_b) * G_b)): the sum of two such filters applied to two image sets of N
- * images each (2N <= the plan's max_images), one C2R.  Replaces the "baseline" mix of
+ * images each (any N; the plan needs max_images >= 2), one C2R per slice.  Replaces the "baseline" mix of
  * src/fusion_net/interpolate_twoframe.py:288-322 -- filter(lab_ada), filter(lab_phase), a DecompValues assembled from the
  * fine levels + low residual of one and the coarse levels + high residual of the other, inv_filter -- which only moves
  * UNMODIFIED values: two full analyses and one full synthesis become two R2C, one multiply-add and one C2R. */

@@ -10,7 +10,11 @@ shape (3 x 64 x 1080 x 1920) with their algorithmic bytes.
 
 --num-img 3 | 4: the same measurements for the pyramid-domain fusion networks: the head adjoint is
 vfi_phasenet_predict_n_backward against the composition over vfi_phasenet_emit_n_backward, the step runs
-PhaseNetCore(num_img).fine_tune(fusion=True) on 3 * num_img images.  The default, 2, prints what it always did."""
+PhaseNetCore(num_img).fine_tune(fusion=True) on 3 * num_img images.  The default, 2, prints what it always did.
+
+--batch B (with --size H W, default 1080 1920): one training step of architecture.PhaseNet on a batch of B samples instead
+(DESIGN.md section 21): img_batch of (num_img + 1) * 3 * B channel-images through one Pyramid.filter call, the walk on 3 * B
+planes, get_loss, backward.  The default, 1, prints what it always did."""
 import argparse
 import math
 import os
@@ -137,11 +141,53 @@ def step(h, w, m, n=3, iters=3, warm=1, batch_stats=False, num_img=2):
     print(f"  backward                   {t_bwd:8.3f} ms = {t_bwd / t_inf:.2f} x that forward")
 
 
+def batch_step(h, w, b, m, iters=5, warm=2, batch_stats=False, num_img=2):
+    """One step of reference src/train/trainer.py:107-134 on B samples: architecture.PhaseNet.forward(img_batch, m=m), get_loss,
+    backward; and its parts that run without a graph."""
+    from vfi_amd.phase_net.architecture import PhaseNet as ArchPhaseNet
+    from vfi_amd.train.loss import get_loss
+    dev = torch.device("cuda:0")
+    height = calc_pyr_height(torch.empty(1, h, w))
+    net = ArchPhaseNet(height, dev, num_img=num_img).fine_tune(batch_stats=batch_stats, fusion=num_img != 2)
+    net.core.load_state_dict(W.net_state(0) if num_img == 2 else FR.net_state(0, num_img))
+    n = (num_img + 1) * 3 * b
+    img_batch = torch.rand((n, h, w), generator=torch.Generator().manual_seed(1)).to(dev)
+    target = img_batch[-3 * b:]
+    m_ = height - 2 if m is None else m
+    with torch.no_grad():
+        t_ana = timed(lambda: net.pyr.filter(img_batch), iters, warm)
+        vals = net.pyr.filter(img_batch)
+        t_syn = timed(lambda: net.pyr.inv_filter(vals), iters, warm)
+        del vals
+        t_inf = timed(lambda: net(img_batch, m=m_), iters, warm)
+
+    def full():
+        net.core.zero_grad(set_to_none=True)
+        prediction, vals_pred, vals_target = net(img_batch, m=m_)
+        get_loss(vals_pred, vals_target, prediction, target, net.pyr)[0].backward()
+    t_step = timed(full, iters, warm)
+    print(f"PhaseNet training step, batch {b} ({n} channel-images, {-(-n // 16)} pyramid slices) {h}x{w}, height {height}, m = {m_}" +
+          (", batch statistics" if batch_stats else "") + (f", num_img = {num_img}" if num_img != 2 else ""))
+    print(f"  analysis of the batch       {t_ana:8.3f} ms")
+    print(f"  synthesis of {n:3d} images     {t_syn:8.3f} ms")
+    print(f"  forward without a graph     {t_inf:8.3f} ms")
+    print(f"  forward + loss + backward   {t_step:8.3f} ms = {t_step / b:.3f} ms per sample")
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("--batch-stats", action="store_true", help="BatchNorm on batch statistics (DESIGN.md section 17)")
     ap.add_argument("--num-img", type=int, choices=(2, 3, 4), default=2, help="input images of the network (DESIGN.md section 20)")
+    ap.add_argument("--batch", type=int, default=1, help="samples per step (DESIGN.md section 21); above 1: architecture.PhaseNet's step on the batch")
+    ap.add_argument("--size", type=int, nargs=2, default=(1080, 1920), metavar=("H", "W"), help="frame size of the --batch step")
     args = ap.parse_args()
+    if args.batch < 1:
+        ap.error("--batch must be at least 1")
+    if args.batch > 1:
+        for m in (None, 4):
+            batch_step(args.size[0], args.size[1], args.batch, m, batch_stats=args.batch_stats, num_img=args.num_img)
+            torch.cuda.empty_cache()
+        return
     if args.batch_stats:
         bn_kernels(1080, 1920)
     elif args.num_img == 2:
