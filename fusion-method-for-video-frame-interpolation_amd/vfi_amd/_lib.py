@@ -110,6 +110,7 @@ SIGNATURES = {
     "vfi_bn_act_backward": [c_f, c_l] * 3 + [c_f, c_f, c_f, c_fl, c_i, c_f, c_l, c_f, c_f, c_f, c_i, c_i, c_i, c_s],
     "vfi_l1_forward": [c_f, c_f, c_l, c_i, c_fl, c_f, c_f, c_s],
     "vfi_l1_backward": [c_f] * 5 + [c_l, c_i, c_fl, c_s],
+    "vfi_triplet_batch_prepare": [c_f, ctypes.c_void_p, c_f, c_l, c_l, c_f, c_l, c_l] + [c_i] * 5 + [c_s],
 }
 REDUCE_WORKSPACE_FLOATS = 4096      # VFI_REDUCE_WORKSPACE_FLOATS
 PHASENET_HEAD_WORKSPACE_FLOATS = 1024 * 520     # VFI_PHASENET_HEAD_WORKSPACE_FLOATS

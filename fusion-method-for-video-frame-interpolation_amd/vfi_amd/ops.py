@@ -992,3 +992,58 @@ def median_filter(x, size):
     out = torch.empty_like(x)
     _lib.call("vfi_median_filter", _lib.dptr(x, "x"), out.data_ptr(), n, h, w, int(size), _lib.stream_ptr())
     return out
+
+
+def _triplet_out(t, name, b, h, w, device):
+    """(address, slot stride, sample stride) of an output of triplet_batch_prepare: (3, B, 3, h, w), or (3, 3B, h, w) for the
+    same layout with dense samples; the (3, h, w) block of a sample is dense, the two outer strides are free."""
+    if t is None:
+        return None, 0, 0
+    if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float32 or t.device != device:
+        raise VfiLibraryError(f"triplet_batch_prepare: {name} must be a float32 tensor on {device}")
+    _lib.check_device(t, name)
+    if t.dim() == 4 and tuple(t.shape) == (3, 3 * b, h, w):
+        t = t.unflatten(1, (b, 3))
+    if t.dim() != 5 or tuple(t.shape) != (3, b, 3, h, w):
+        raise VfiLibraryError(f"triplet_batch_prepare: {name} must be (3, {b}, 3, {h}, {w}) or (3, {3 * b}, {h}, {w}), "
+                              f"got {tuple(t.shape)}")
+    s0, s1, sc, sh, sw = t.stride()
+    if not ((sw == 1 or w == 1) and (sh == w or h == 1) and sc == h * w):
+        raise VfiLibraryError(f"triplet_batch_prepare: {name}: a sample's (3,h,w) block must be dense, strides {t.stride()}")
+    return t.data_ptr(), s0, (s1 if b > 1 else 3 * h * w)
+
+
+def triplet_batch_prepare(src, params, size, rgb=True, lab=True):
+    """One training batch from decoded frames (vfi_triplet_batch_prepare; reference src/train/datareader.py:45-69 and
+    src/train/trainer.py:115-121, :103).
+    src: uint8 (B, 3, Hs, Ws, 3) on the device: im1, im2, im3 of each sample, HWC.  params: int32 (B, 3) ON THE HOST =
+    (crop row, crop column, flags: 1 hflip | 2 vflip | 4 temporal swap).  size = (h, w) of the crop.
+    rgb / lab: True = a new tensor, None / False = not wanted, or a float32 tensor to write into (a slice of a wider buffer).
+    -> (rgb (3, B, 3, h, w) = [first, last, middle frame] / 255, lab (3, 3B, h, w) = preprocess of each slot), None where
+    not wanted."""
+    if not isinstance(src, torch.Tensor) or not src.is_cuda:
+        raise VfiLibraryError("triplet_batch_prepare: src must be a tensor on a HIP device (vfi_amd has no CPU path)")
+    if src.dtype != torch.uint8 or src.dim() != 5 or src.shape[1] != 3 or src.shape[4] != 3:
+        raise VfiLibraryError(f"triplet_batch_prepare: src must be uint8 (B, 3, Hs, Ws, 3), got {src.dtype} {tuple(src.shape)}")
+    b, _, hs, ws, _ = src.shape
+    h, w = int(size[0]), int(size[1])
+    params = torch.as_tensor(params)
+    if params.is_cuda or params.dtype != torch.int32 or tuple(params.shape) != (b, 3):
+        raise VfiLibraryError(f"triplet_batch_prepare: params must be a host int32 tensor of shape ({b}, 3)")
+    params = params.contiguous()
+    if h <= 0 or w <= 0:
+        raise VfiLibraryError(f"triplet_batch_prepare: bad crop size {h}x{w}")
+    if rgb is True:
+        rgb = torch.empty((3, b, 3, h, w), dtype=torch.float32, device=src.device)
+    elif rgb is False:
+        rgb = None
+    if lab is True:
+        lab = torch.empty((3, 3 * b, h, w), dtype=torch.float32, device=src.device)
+    elif lab is False:
+        lab = None
+    rp, rs, rb = _triplet_out(rgb, "rgb", b, h, w, src.device)
+    lp, ls, lb = _triplet_out(lab, "lab", b, h, w, src.device)
+    moved = 3 * b * h * w * (3 + 12 * (rgb is not None) + 12 * (lab is not None))
+    _lib.call("vfi_triplet_batch_prepare", _lib.dptr(src, "src", torch.uint8), params.data_ptr(), rp, rs, rb, lp, ls, lb,
+              b, hs, ws, h, w, _lib.stream_ptr(), work=("byte", float(moved), "triplet_batch_prepare"))
+    return rgb, lab

@@ -786,6 +786,29 @@ int vfi_mul(const float *a, const float *b, float *out, long long count, vfi_str
  * (called at src/evaluation/evaluate_image.py:21) for images whose short side exceeds 384 px. */
 int vfi_avg_pool(const float *x, float *y, int planes, int H, int W, int f, vfi_stream_t stream);
 
+/* ------------------------------------------------------------------------------------
+ * Training input side
+ * ---------------------------------------------------------------------------------- */
+
+/* One batch of Vimeo triplets from decoded uint8 frames to the tensors a training step takes: the host-side crop / hflip /
+ * vflip / temporal swap of DBreader_Vimeo90k.__getitem__ (src/train/datareader.py:45-69), ToTensor's / 255, and
+ * `preprocess` of the three frames (src/train/utils.py:174-206, called at src/train/trainer.py:115-117), in one pass.
+ *   src     DEVICE uint8 (B, 3, Hs, Ws, 3): im1, im2, im3 of each sample, HWC as decoded; rows of 3 * Ws bytes, any alignment
+ *   params  HOST int32 (B, 3) = (crop row i, crop column j, flags), read and checked before anything is enqueued and baked
+ *           into the launch (a captured graph replays them); flags: bit 0 hflip, bit 1 vflip, bit 2 temporal swap
+ *           (im3 takes im1's place and the other way round).  Order as the reference: crop, hflip, vflip.
+ *   rgb     (3, B, 3, h, w) float32 or NULL: slot s = [first frame, last frame, middle frame] after the swap;
+ *           rgb[s][b][c][y][x] = source byte / 255, bit-identical to `uint8.float() / 255`;
+ *           element strides rgb_slot_stride (between slots) and rgb_batch_stride (between samples), the (3, h, w) block dense
+ *   lab     (3, 3B, h, w) float32 or NULL: lab[s] = preprocess(rgb[s]), sample-major then L, a, b (vfi_rgb2lab's formulas
+ *           and accuracy); lab_slot_stride between slots, lab_batch_stride between the (3, h, w) blocks of two samples.
+ *           Dense, (9B, h, w) is the `torch.cat((lab_frame1, lab_frame2, target), 0)` of trainer.py:103.
+ * VFI_ERR_INVALID_ARG, with nothing written: i < 0, i + h > Hs, j < 0, j + w > Ws, flags outside 0..7, both outputs NULL,
+ * a stride below 3 * h * w.  One launch per 64 samples. */
+int vfi_triplet_batch_prepare(const unsigned char *src, const int *params, float *rgb, long long rgb_slot_stride,
+                              long long rgb_batch_stride, float *lab, long long lab_slot_stride, long long lab_batch_stride,
+                              int B, int Hs, int Ws, int h, int w, vfi_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
