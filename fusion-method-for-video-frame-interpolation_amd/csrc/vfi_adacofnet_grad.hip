@@ -378,3 +378,20 @@ extern "C" int vfi_charbonnier_backward(const float *a, const float *b, const fl
               grad_b, count, (float)(1.0 / (double)count));
     return vfi::check_launch("vfi_charbonnier_backward");
 }
+
+extern "C" int vfi_mse_forward(const float *a, const float *b, long long count, float *workspace, float *out,
+                               vfi_stream_t stream) {
+    VFI_REQUIRE(a && b && workspace && out, VFI_ERR_INVALID_ARG, "vfi_mse_forward: null pointer");
+    VFI_REQUIRE(count > 0, VFI_ERR_INVALID_ARG, "vfi_mse_forward: bad size");
+    // nn.MSELoss (losses/__init__.py:17, losses/vgg.py:20)
+    return launch_sum_forward(SquareTerm{}, a, b, count, (float)(1.0 / (double)count), workspace, out, stream, "vfi_mse_forward");
+}
+
+extern "C" int vfi_mse_backward(const float *a, const float *b, const float *upstream, float *grad_a, float *grad_b,
+                                long long count, vfi_stream_t stream) {
+    VFI_REQUIRE(a && b && upstream && (grad_a || grad_b), VFI_ERR_INVALID_ARG, "vfi_mse_backward: null pointer");
+    VFI_REQUIRE(count > 0, VFI_ERR_INVALID_ARG, "vfi_mse_backward: bad size");
+    LAUNCH_1D(sum_backward_kernel<SquareTerm>, count, stream, SquareTerm{}, a, b, upstream, grad_a, grad_b, count,
+              (float)(1.0 / (double)count));
+    return vfi::check_launch("vfi_mse_backward");
+}

@@ -104,6 +104,10 @@ struct CharbonnierTerm {        // sqrt(d^2 + e^2)
     __device__ __forceinline__ float operator()(float d) const { return sqrtf(d * d + eps2); }
     __device__ __forceinline__ float grad(float d, float s) const { return s * d * rsqrtf(d * d + eps2); }
 };
+struct SquareTerm {             // d^2 (nn.MSELoss)
+    __device__ __forceinline__ float operator()(float d) const { return d * d; }
+    __device__ __forceinline__ float grad(float d, float s) const { return 2.0f * s * d; }
+};
 // |wrap(d)|, wrap(d) = atan2(sin d, cos d): d brought to (-pi, pi] (the phase loss); |d| without WRAP
 template <bool WRAP> struct AbsTerm {
     __device__ __forceinline__ float wrapped(float d) const { return WRAP ? atan2f(sinf(d), cosf(d)) : d; }

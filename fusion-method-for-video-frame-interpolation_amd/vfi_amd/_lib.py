@@ -97,6 +97,8 @@ SIGNATURES = {
     "vfi_adacof_head_backward": [c_f] * 8 + [c_l] + [c_f] * 4 + [c_i] * 4 + [c_fl, c_s],
     "vfi_charbonnier_forward": [c_f, c_f, c_l, c_fl, c_f, c_f, c_s],
     "vfi_charbonnier_backward": [c_f] * 5 + [c_l, c_fl, c_s],
+    "vfi_mse_forward": [c_f, c_f, c_l, c_f, c_f, c_s],
+    "vfi_mse_backward": [c_f] * 5 + [c_l, c_s],
     "vfi_resize_bilinear_adjoint": [c_f, c_l] * 2 + [c_i] * 6 + [c_s],
     "vfi_act_backward": [c_f, c_l] * 3 + [c_i, c_l, c_i, c_s],
     "vfi_phasenet_emit_backward": [c_f, c_f, c_f, c_l, c_f, c_f, c_l, c_i, c_i, c_s],

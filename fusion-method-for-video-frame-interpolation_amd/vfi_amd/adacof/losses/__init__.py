@@ -1,0 +1,139 @@
+"""Loss of the AdaCoF trainer -- mirror of reference src/adacof/losses/__init__.py:6-72 (same class, same `weight*type`
+grammar joined by `+`, same printed lines, same summation order).
+
+`Loss(args)` reads `args.loss`; `forward(output, gt, input_frames)` takes the training dict of the network
+({'frame1', 'g_Spatial', 'g_Occlusion'}), the target and the two input frames, and returns
+`sum([w_0 * l_0(frame1, gt), ..., w_r * output[r], ...])` -- Python's `sum`, which starts from the int 0, terms first and
+regularisers after them, each group in the order of the string.
+
+`Module_MSELoss` / `Module_L1Loss` stand for the reference's `nn.MSELoss()` / `nn.L1Loss()`: one HIP autograd node each
+(`vfi_mse_*`, `vfi_l1_*` with wrap off and scale 1: the fixed-order two-stage reduction of the Charbonnier node, one
+streaming pass backward) when `utility._on_hip` holds, the plain torch expression otherwise.
+
+Differences from the reference:
+
+* `VGG` (losses/vgg.py) takes its weights from a file the user has -- `args.vgg_weights`, default the environment variable
+  `VFI_VGG16_WEIGHTS` -- instead of downloading them; see vgg.py.
+* A type containing `GAN` raises NotImplementedError: the discriminators (losses/discriminator.py, adversarial.py) are not
+  built.  Any other unknown type raises ValueError; the reference fails there on an unbound name.
+* The modules move to `cuda:<args.gpu_id>` (the reference: 'cuda', after `set_device(gpu_id)`), and stay where they are when
+  there is no device, so the string can be parsed on a host.
+"""
+import os
+
+import torch
+import torch.nn as nn
+import torch.nn.functional as F
+
+from ... import ops
+from ..utility import Module_CharbonnierLoss, _on_hip
+
+REGULARIZERS = ('g_Spatial', 'g_Occlusion', 'Lw', 'Ls')
+VGG_WEIGHTS_ENV = 'VFI_VGG16_WEIGHTS'
+
+
+class _Mean(torch.autograd.Function):
+    """mean(term(a - b)) as one node; term: 'mse' | 'l1'."""
+
+    @staticmethod
+    def forward(ctx, a, b, term):
+        a, b = a.contiguous(), b.contiguous()
+        ctx.term = term
+        ctx.save_for_backward(a, b)
+        return ops.mse_forward(a, b) if term == 'mse' else ops.l1_forward(a, b, wrap=False, scale=1.0)
+
+    @staticmethod
+    def backward(ctx, upstream):
+        a, b = ctx.saved_tensors
+        need_a, need_b = ctx.needs_input_grad[:2]
+        if ctx.term == 'mse':
+            ga, gb = ops.mse_backward(a, b, upstream.contiguous(), need_a=need_a, need_b=need_b)
+        else:
+            ga, gb = ops.l1_backward(a, b, upstream.contiguous(), wrap=False, scale=1.0, need_a=need_a, need_b=need_b)
+        return ga, gb, None
+
+
+def _mean(a, b, term):
+    if a.shape != b.shape:
+        a, b = torch.broadcast_tensors(a, b)
+    if _on_hip(a, b):
+        return _Mean.apply(a, b, term)
+    return F.mse_loss(a, b) if term == 'mse' else F.l1_loss(a, b)
+
+
+class Module_MSELoss(nn.Module):
+    """mean((output - gt)^2): nn.MSELoss() (losses/__init__.py:17)."""
+
+    def forward(self, output, gt):
+        return _mean(output, gt, 'mse')
+
+
+class Module_L1Loss(nn.Module):
+    """mean(|output - gt|): nn.L1Loss() (losses/__init__.py:19)."""
+
+    def forward(self, output, gt):
+        return _mean(output, gt, 'l1')
+
+
+class Loss(nn.modules.loss._Loss):
+    def __init__(self, args):
+        super(Loss, self).__init__()
+
+        self.loss = []
+        self.loss_module = nn.ModuleList()
+        self.regularize = []
+
+        for loss in args.loss.split('+'):
+            weight, loss_type = loss.split('*')
+            if loss_type == 'MSE':
+                loss_function = Module_MSELoss()
+            elif loss_type == 'L1':
+                loss_function = Module_L1Loss()
+            elif loss_type == 'Charb':
+                loss_function = Module_CharbonnierLoss()
+            elif loss_type.find('VGG') >= 0:
+                from .vgg import VGG
+                loss_function = VGG(weights=getattr(args, 'vgg_weights', None) or os.environ.get(VGG_WEIGHTS_ENV))
+            elif loss_type.find('GAN') >= 0:
+                raise NotImplementedError(f"loss type {loss_type!r}: the adversarial terms need the reference's "
+                                          "discriminator, which is not built")
+            elif loss_type in REGULARIZERS:
+                self.regularize.append({
+                    'type': loss_type,
+                    'weight': float(weight)}
+                )
+                continue
+            else:
+                raise ValueError(f"unknown loss type {loss_type!r} in {args.loss!r}")
+
+            self.loss.append({
+                'type': loss_type,
+                'weight': float(weight),
+                'function': loss_function}
+            )
+
+        for l in self.loss:
+            if l['function'] is not None:
+                print('{:.3f} * {}'.format(l['weight'], l['type']))
+                self.loss_module.append(l['function'])
+
+        for r in self.regularize:
+            print('{:.3f} * {}'.format(r['weight'], r['type']))
+
+        if torch.cuda.is_available():
+            self.loss_module.to('cuda:{}'.format(getattr(args, 'gpu_id', torch.cuda.current_device())))
+
+    def forward(self, output, gt, input_frames):
+        losses = []
+        for l in self.loss:
+            if l['function'] is not None:
+                loss = l['function'](output['frame1'], gt)
+                effective_loss = l['weight'] * loss
+                losses.append(effective_loss)
+
+        for r in self.regularize:
+            effective_loss = r['weight'] * output[r['type']]
+            losses.append(effective_loss)
+        loss_sum = sum(losses)
+
+        return loss_sum

@@ -3,8 +3,8 @@
 `CharbonnierFunc` / `Module_CharbonnierLoss` (utility.py:67-77) run as one HIP autograd node (a fixed-order two-stage
 reduction forward, one streaming pass backward) when they are given HIP tensors of which one requires grad, so the
 reference loss `1*Charb` on `output['frame1']` stays off torch's elementwise kernels; any other argument (CPU tensors,
-float64, nothing requiring grad) takes the plain torch expression.  The VGG and GAN losses need downloaded weights and
-are not mirrored.
+float64, nothing requiring grad) takes the plain torch expression (`_on_hip` decides, for the MSE / L1 nodes of
+`losses/__init__.py` too).  The trainer's `Loss` and its VGG term are in `losses/`; the GAN terms are not mirrored.
 """
 import torch
 import torch.nn as nn

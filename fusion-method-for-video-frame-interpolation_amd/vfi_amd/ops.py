@@ -543,6 +543,27 @@ def charbonnier_backward(a, b, upstream, epsilon=0.001, need_a=True, need_b=Fals
     return ga, gb
 
 
+def mse_forward(a, b):
+    """mean((a - b)^2) -> 0-dim tensor (nn.MSELoss); a and b dense, of one element count, possibly parts of one tensor."""
+    if a.numel() != b.numel():
+        raise VfiLibraryError("mse_forward: shape mismatch")
+    out = new((1,), a)
+    _lib.call("vfi_mse_forward", _lib.dptr(a, "a"), _lib.dptr(b, "b"), a.numel(), _reduce_workspace(a).data_ptr(),
+              out.data_ptr(), _lib.stream_ptr(), work=_prof("byte", 8.0 * a.numel(), "mse_forward"))
+    return out[0]
+
+
+def mse_backward(a, b, upstream, need_a=True, need_b=False):
+    if a.numel() != b.numel():
+        raise VfiLibraryError("mse_backward: shape mismatch")
+    ga = torch.empty_like(a) if need_a else None
+    gb = torch.empty_like(b) if need_b else None
+    _lib.call("vfi_mse_backward", _lib.dptr(a, "a"), _lib.dptr(b, "b"), _lib.dptr(upstream.reshape(1), "upstream"),
+              _lib.dptr(ga), _lib.dptr(gb), a.numel(), _lib.stream_ptr(),
+              work=_prof("byte", 4.0 * a.numel() * (2 + need_a + need_b), "mse_backward"))
+    return ga, gb
+
+
 # ---- glue of a PhaseNet level's backward (DESIGN.md section 14) -----------------------------------------------------
 def resize_bilinear_adjoint(grad, size, out=None):
     """Adjoint of resize_bilinear(x, grad's size, align_corners=False) for x of spatial `size` (any sizes; gather form)."""

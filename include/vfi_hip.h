@@ -459,6 +459,14 @@ int vfi_charbonnier_forward(const float *a, const float *b, long long count, flo
 int vfi_charbonnier_backward(const float *a, const float *b, const float *upstream, float *grad_a, float *grad_b,
                              long long count, float epsilon, vfi_stream_t stream);
 
+/* out[0] = mean (a - b)^2 over `count` floats (nn.MSELoss: src/adacof/losses/__init__.py:17, losses/vgg.py:20).  a and b may
+ * be two parts of one allocation.  Two-stage reduction over `workspace` (VFI_REDUCE_WORKSPACE_FLOATS). */
+int vfi_mse_forward(const float *a, const float *b, long long count, float *workspace, float *out, vfi_stream_t stream);
+
+/* grad_a = upstream[0] * 2 (a - b) / count, grad_b = -grad_a; either may be NULL. */
+int vfi_mse_backward(const float *a, const float *b, const float *upstream, float *grad_a, float *grad_b, long long count,
+                     vfi_stream_t stream);
+
 /* ------------------------------------------------------------------------------------
  * Backward of one PhaseNet level (training, src/phase_net/train.py with src/train/loss.py): the glue between the
  * convolution gradients above.  Differentiates src/phase_net/phase_net.py:113-116,138-139,155-168,190-200 with

@@ -3,7 +3,13 @@
 src/adacof/train.py): inference forward, training forward (activations kept), the HIP backward split by per-call HIP events
 into weight gradients, input gradients, sampler and glue, and each new streaming kernel's effective TB/s (to be read
 against profiles/r04_hbm_rates.txt: vfi_resize_bilinear 4.1-4.5 TB/s, plain copy 4.75-5.3 TB/s).  The same
-KernelEstimation as plain torch.nn layers (MIOpen convolutions) on the same GPU is timed for context."""
+KernelEstimation as plain torch.nn layers (MIOpen convolutions) on the same GPU is timed for context.
+
+`--loss STRING` adds the trainer's step with that `vfi_amd.adacof.losses.Loss` (forward, loss, backward, Adamax step) next
+to the default loss's, and, when the string has a VGG term, the VGG node alone (forward, backward to the image) and torch's
+own nn.Sequential of the same ten layers (MIOpen), forward + backward to the input.  `--vgg-weights FILE` is a torchvision
+vgg16 state dict; without it seeded He-scaled weights are used (the time does not depend on the values)."""
+import argparse
 import os
 import sys
 import types
@@ -30,7 +36,67 @@ def timed(fn, iters, warm):
     return e0.elapsed_time(e1) / iters
 
 
-def main(n=4, h=256, w=256, iters=10, warm=3):
+DEFAULT_LOSS = "1*Charb+0.01*g_Spatial+0.005*g_Occlusion"
+
+
+def seeded_vgg16_state(seed=0):
+    """He-scaled weights under torchvision's keys features.{0,...,21}.{weight,bias}"""
+    from vfi_amd.adacof.losses import vgg
+    g = torch.Generator().manual_seed(seed)
+    sd = {}
+    for i, idx in enumerate(vgg.CONV_INDICES):
+        cin, cout = vgg.CHANNELS[i], vgg.CHANNELS[i + 1]
+        sd[f"features.{idx}.weight"] = torch.randn((cout, cin, 3, 3), generator=g) * (2.0 / (9 * cin)) ** 0.5
+        sd[f"features.{idx}.bias"] = torch.randn((cout,), generator=g) * 0.05
+    return sd
+
+
+def loss_section(net, f0, f1, f2, loss_string, vgg_weights, iters, warm):
+    from vfi_amd.adacof import losses, utility
+    from vfi_amd.adacof.losses import vgg
+    weights = vgg_weights or seeded_vgg16_state()
+    opt_args = types.SimpleNamespace(optimizer="ADAMax", lr=1e-3, weight_decay=0)
+    net.train(True)
+    for string in dict.fromkeys((DEFAULT_LOSS, loss_string)):
+        crit = losses.Loss(types.SimpleNamespace(loss=string, vgg_weights=weights, gpu_id=0))
+        opt = utility.make_optimizer(opt_args, net)
+
+        def step():
+            opt.zero_grad()
+            crit(net(f0, f2), f1, [f0, f2]).backward()
+            opt.step()
+        print(f"  trainer step, --loss {string}: {timed(step, iters, warm):8.3f} ms")
+    if "VGG" not in loss_string:
+        return
+    node = vgg.VGG(weights).to(f0.device)
+    x = f0.clone().requires_grad_(True)
+    t_f = timed(lambda: node(x, f1), iters, warm)
+
+    def vstep():
+        x.grad = None
+        node(x, f1).backward()
+    t_s = timed(vstep, iters, warm)
+    print(f"  VGG node alone: forward {t_f:.3f} ms, backward {t_s - t_f:.3f} ms")
+    seq = vgg._sequential().to(f0.device)
+    seq.load_state_dict(node.vgg16_conv_4_3.state_dict())
+    for p in seq.parameters():
+        p.requires_grad = False
+    import torch.nn.functional as F
+
+    def tloss():
+        with torch.no_grad():
+            t = seq(f1)
+        return F.mse_loss(seq(x), t)
+    t_tf = timed(tloss, iters, warm)
+
+    def tstep():
+        x.grad = None
+        tloss().backward()
+    t_ts = timed(tstep, iters, warm)
+    print(f"  torch/MIOpen nn.Sequential of the ten layers: forward {t_tf:.3f} ms, backward {t_ts - t_tf:.3f} ms")
+
+
+def main(n=4, h=256, w=256, iters=10, warm=3, loss_string=None, vgg_weights=None):
     dev = torch.device("cuda:0")
     sd = nets_cpu.adacofnet_random_state_dict(0)
     net = AdaCoFNet(types.SimpleNamespace(kernel_size=5, dilation=1, gpu_id=0)).to(dev)
@@ -114,5 +180,14 @@ def main(n=4, h=256, w=256, iters=10, warm=3):
           f"backward {t_tstep - t_tfwd:.3f} ms")
 
 
+    if loss_string:
+        f1 = torch.rand((n, 3, h, w), generator=g).to(dev)
+        loss_section(net, f0, f1, f2, loss_string, vgg_weights, iters, warm)
+
+
 if __name__ == "__main__":
-    main()
+    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    ap.add_argument("--loss", default=None, help="also time the trainer's step with this loss string")
+    ap.add_argument("--vgg-weights", default=None, help="torchvision vgg16 state dict (default: seeded weights)")
+    a = ap.parse_args()
+    main(loss_string=a.loss, vgg_weights=a.vgg_weights)
