@@ -14,6 +14,9 @@ Differences from the reference:
 
 * `VGG` (losses/vgg.py) takes its weights from a file the user has -- `args.vgg_weights`, default the environment variable
   `VFI_VGG16_WEIGHTS` -- instead of downloading them; see vgg.py.
+* The type `LPIPS` (not in the reference's grammar, e.g. `1*Charb+0.1*LPIPS`) is the mean over the batch of
+  `vfi_amd.evaluation.lpips.LPIPS`, with `args.vgg_weights` as above and its head weights from `args.lpips_weights`,
+  default `VFI_LPIPS_WEIGHTS`.  It is matched before the `VGG` substring test.
 * A type containing `GAN` raises NotImplementedError: the discriminators (losses/discriminator.py, adversarial.py) are not
   built.  Any other unknown type raises ValueError; the reference fails there on an unbound name.
 * The modules move to `cuda:<args.gpu_id>` (the reference: 'cuda', after `set_device(gpu_id)`), and stay where they are when
@@ -30,6 +33,7 @@ from ..utility import Module_CharbonnierLoss, _on_hip
 
 REGULARIZERS = ('g_Spatial', 'g_Occlusion', 'Lw', 'Ls')
 VGG_WEIGHTS_ENV = 'VFI_VGG16_WEIGHTS'
+LPIPS_WEIGHTS_ENV = 'VFI_LPIPS_WEIGHTS'
 
 
 class _Mean(torch.autograd.Function):
@@ -91,6 +95,11 @@ class Loss(nn.modules.loss._Loss):
                 loss_function = Module_L1Loss()
             elif loss_type == 'Charb':
                 loss_function = Module_CharbonnierLoss()
+            elif loss_type == 'LPIPS':
+                from ...evaluation.lpips import LPIPS
+                loss_function = LPIPS(getattr(args, 'vgg_weights', None) or os.environ.get(VGG_WEIGHTS_ENV),
+                                      getattr(args, 'lpips_weights', None) or os.environ.get(LPIPS_WEIGHTS_ENV),
+                                      reduction='mean')
             elif loss_type.find('VGG') >= 0:
                 from .vgg import VGG
                 loss_function = VGG(weights=getattr(args, 'vgg_weights', None) or os.environ.get(VGG_WEIGHTS_ENV))

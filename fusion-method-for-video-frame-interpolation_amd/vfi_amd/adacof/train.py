@@ -2,7 +2,8 @@
 `python -m vfi_amd.adacof.train --train <vimeo_triplet> --test_input <middlebury input> --gt <middlebury gt> ...`.
 
 The reference's flags and defaults, plus `--vgg_weights` (a torchvision vgg16 state dict for a `VGG` term of `--loss`;
-default: the environment variable VFI_VGG16_WEIGHTS) and `--workers` (decoding threads of TripletLoader).
+default: the environment variable VFI_VGG16_WEIGHTS), `--lpips_weights` (the head weights of an `LPIPS` term, which reads
+`--vgg_weights` too; default: VFI_LPIPS_WEIGHTS) and `--workers` (decoding threads of TripletLoader).
 
 Differences from the reference:
 
@@ -46,6 +47,8 @@ parser.add_argument('--loss', type=str, default='1*Charb+0.01*g_Spatial+0.005*g_
 parser.add_argument('--patch_size', type=int, default=256, help='Patch size')
 parser.add_argument('--vgg_weights', type=str, default=os.environ.get(losses.VGG_WEIGHTS_ENV),
                     help='torchvision vgg16 state dict for a VGG term (default: $VFI_VGG16_WEIGHTS)')
+parser.add_argument('--lpips_weights', type=str, default=os.environ.get(losses.LPIPS_WEIGHTS_ENV),
+                    help='LPIPS head weights for an LPIPS term (default: $VFI_LPIPS_WEIGHTS)')
 parser.add_argument('--workers', type=int, default=4, help='decoding threads')
 
 # Optimization specifications

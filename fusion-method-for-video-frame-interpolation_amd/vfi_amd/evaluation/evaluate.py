@@ -10,8 +10,9 @@ Same flags and flow as the reference (`parser` :28-73, `eval` :219-278):
   3. per test set: `evaluate_dataset` (:76-212) scores every prediction against the ground-truth frame
      Testset/<set>/<i>.png with `evaluate_image` and caches the array as <base_dir>/result_<set>.npy (:266-278).
 Differences in execution, not results: predictions and targets are decoded to the GPU and scored there
-(vfi_amd.evaluation.evaluate_image: PSNR/SSIM/ad-hoc measures as deterministic device reductions; LPIPS column NaN --
-needs pretrained VGG weights that ship neither with the reference nor with this image); with torch.distributed
+(vfi_amd.evaluation.evaluate_image: PSNR/SSIM/ad-hoc measures as deterministic device reductions; LPIPS from
+vfi_amd.evaluation.lpips when --vgg_weights and --lpips_weights name the pretrained files, which ship neither with the
+reference nor with this project -- without them the column is NaN); with torch.distributed
 initialised (one process per GPU, rank r on GPU LOCAL_RANK) the test sets are dealt round-robin to the ranks -- no
 collective: every rank writes its own result_<set>.npy and the caches make a second pass on any rank complete; an
 explicit --base_dir is required then, and a set without predictions raises instead of caching an empty array.  The matplotlib figures of
@@ -32,6 +33,7 @@ from .. import shard
 from ..adacof.models import Model
 from ..fusion_net.fusion_net import FusionNet
 from . import evaluate_image, interpolate
+from .lpips import LPIPS, LPIPS_WEIGHTS_ENV, VGG_WEIGHTS_ENV
 
 MEASURES = ("ssim", "lpips", "psnr", "ssd", "l1", "mse", "variance")       # evaluate_image.py:30 order
 
@@ -72,6 +74,9 @@ parser.add_argument("--fusion_replace_high_level", action="store_true")
 parser.add_argument("--vimeo_testset", action="store_true")
 parser.add_argument("--mode", type=str, default="alpha")
 parser.add_argument("--dim", type=int, default=512)
+# LPIPS column: a torchvision vgg16 state dict and the head weights (piq's file or the lpips package's), see lpips.py
+parser.add_argument("--vgg_weights", type=str, default=os.environ.get(VGG_WEIGHTS_ENV))
+parser.add_argument("--lpips_weights", type=str, default=os.environ.get(LPIPS_WEIGHTS_ENV))
 
 
 def _to_tensor(path, device):
@@ -134,6 +139,16 @@ def build_models(args):
     return adacof_model, fusion_net
 
 
+def build_lpips(args):
+    """The LPIPS module of the metric column, built once in eval(); None (the column stays NaN) without both files."""
+    vgg, head = getattr(args, "vgg_weights", None), getattr(args, "lpips_weights", None)
+    if not (vgg and head):
+        print("evaluate: no LPIPS (needs --vgg_weights and --lpips_weights, or {} and {}): that column is NaN".format(
+            VGG_WEIGHTS_ENV, LPIPS_WEIGHTS_ENV))
+        return None
+    return LPIPS(vgg, head, reduction="none").to(torch.device("cuda:{}".format(args.gpu_id))).eval()
+
+
 def _run_token():
     """What the ranks of ONE launch share and no other launch has: torchrun's run id and rendezvous port.  The hand-off
     marker carries it, so a marker left behind in a reused --base_dir is never taken for this run's."""
@@ -172,6 +187,8 @@ def eval(args, rank=None, world=None):           # noqa: A001  (the reference's 
     img_output_dir = os.path.join(args.base_dir, args.img_output)
     os.makedirs(img_output_dir, exist_ok=True)
     adacof_model, fusion_net = build_models(args)
+    if not isinstance(getattr(args, "lpips", None), torch.nn.Module):
+        args.lpips = build_lpips(args)
     if getattr(args, "vimeo_testset", False):
         # the triplet list is one flat file: rank 0 interpolates it, the others wait for its marker before they score
         marker = os.path.join(img_output_dir, ".vimeo_interpolated." + _run_token())
@@ -207,7 +224,7 @@ def eval(args, rank=None, world=None):           # noqa: A001  (the reference's 
         if result_np.size:
             with warnings.catch_warnings():
                 warnings.simplefilter("ignore", RuntimeWarning)
-                mean = np.nanmean(result_np, axis=0)                                  # (methods, 7); LPIPS column stays NaN
+                mean = np.nanmean(result_np, axis=0)                                  # (methods, 7); LPIPS column NaN without its weights
             for m, row in enumerate(mean):
                 print("Result for {} [method {}]: ".format(testset, m) +
                       "  ".join("{} {:.5g}".format(k, v) for k, v in zip(MEASURES, row)))

@@ -7,8 +7,9 @@
     of the difference, evaluate_image.py:25-26);
   * ssim  -- piq.ssim defaults (11-tap Gaussian sigma 1.5, valid region, k1=0.01, k2=0.03, average-pool downsample by
     max(1, round(min(H,W)/256))): restated from piq's published formula (piq is absent here: PARITY UNPINNED);
-  * lpips -- needs piq's pretrained VGG16 + linear-head weights, which exist neither in the reference tree nor in
-    this image (no network): the column is NaN, and vfi_amd.evaluation.evaluate aggregates NaN-aware.
+  * lpips -- piq.LPIPS(reduction='none') on the device (vfi_amd.evaluation.lpips: PARITY UNPINNED) when `args.lpips` holds
+    that module; it needs pretrained VGG16 and head weights from files of the user's, so without it the column is NaN,
+    and vfi_amd.evaluation.evaluate aggregates NaN-aware.
 All reductions are deterministic (fixed-order double accumulation in libvfi_hip.so)."""
 import math
 
@@ -64,4 +65,9 @@ def evaluate_image(args, prediction_im, target_im):
     n = p.numel()
     mean = s1 / n
     var = (s2 - n * mean * mean) / (n - 1)                      # torch.var: unbiased
-    return np.array([ssim(p, t), float("nan"), 10.0 * math.log10(1.0 / (s2 / n + 1e-8)), math.sqrt(s2), s1, mean, var])
+    net = getattr(args, "lpips", None)
+    lpips = float("nan")
+    if isinstance(net, torch.nn.Module):
+        with torch.no_grad():
+            lpips = float(net(p.unsqueeze(0), t.unsqueeze(0)).reshape(-1)[0])
+    return np.array([ssim(p, t), lpips, 10.0 * math.log10(1.0 / (s2 / n + 1e-8)), math.sqrt(s2), s1, mean, var])

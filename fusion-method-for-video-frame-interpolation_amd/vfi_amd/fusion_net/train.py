@@ -3,12 +3,14 @@
 
 The reference's flags and defaults, plus `--out_dir` (default: the reference's `./output_fusion_net_3_no_uncertainty_map`),
 `--crop H W` (256 256), `--height` (12), `--workers`, `--phasenet_checkpoint`, `--adacof_checkpoint` (defaults: the
-reference's paths) and `--test_paths A B C`.  `--save` is accepted and raises NotImplementedError (trainer.py).
+reference's paths), `--test_paths A B C`, and `--lpips_weight` (0) with `--vgg_weights` / `--lpips_weights` (defaults: the
+environment variables VFI_VGG16_WEIGHTS / VFI_LPIPS_WEIGHTS) for the perceptual term of trainer.py.  `--save` is accepted and raises NotImplementedError (trainer.py).
 
 The network is `FusionNet(kernel, pad, dil)` with its default three uncertainty maps, which `Trainer.predict` feeds it; the
 reference's script builds `FusionNet(uncertainty_maps=0)` (train.py:79), whose first convolution has three input channels
 fewer than its own forward concatenates."""
 import argparse
+import os
 import random
 
 import numpy as np
@@ -56,6 +58,13 @@ parser.add_argument('--pad', type=int, default=3, help='Padding for kernel size'
 parser.add_argument('--phasenet_checkpoint', type=str, default='src/phase_net/phase_net.pt')
 parser.add_argument('--adacof_checkpoint', type=str, default=ADACOF_CHECKPOINT)
 parser.add_argument('--test_paths', type=str, nargs=3, default=None, metavar=('A', 'B', 'C'))
+
+# Perceptual term: loss = l1 + lpips_weight * mean LPIPS(clip(prediction), target)
+parser.add_argument('--lpips_weight', type=float, default=0.0, help='weight of the LPIPS term (0: none)')
+parser.add_argument('--vgg_weights', type=str, default=os.environ.get('VFI_VGG16_WEIGHTS'),
+                    help='torchvision vgg16 state dict (default: $VFI_VGG16_WEIGHTS)')
+parser.add_argument('--lpips_weights', type=str, default=os.environ.get('VFI_LPIPS_WEIGHTS'),
+                    help='LPIPS head weights (default: $VFI_LPIPS_WEIGHTS)')
 
 
 def main(argv=None):

@@ -3,8 +3,10 @@
 `Trainer(args, train_loader, fusion_net, phase_net, adacof_model, my_pyr, lr, weight_decay, start_epoch, out_dir)`; only
 `fusion_net` is trained (Adam on its parameters); PhaseNet and AdaCoF produce its inputs under no_grad through
 `train_batch.fusion_net_inputs`, which is the reference's `predict` up to the call of the network.  The loss is
-`l1(target_rgb, clip(final, 0, 1))` (trainer.py:246-254).  `train_loader` yields `datareader.TripletBatch`es, or the
-reference's triples of (B, 3, h, w) CPU tensors.
+`l1(target_rgb, clip(final, 0, 1))` (trainer.py:246-254), plus `args.lpips_weight * mean LPIPS(clip(final, 0, 1), target_rgb)`
+when that weight is not 0 (evaluation/lpips.py, built from `args.vgg_weights` and `args.lpips_weights`; the reference imports
+LPIPS at trainer.py:13 and trains with L1 alone); at 0 nothing is built and the step is the reference's.  `train_loader`
+yields `datareader.TripletBatch`es, or the reference's triples of (B, 3, h, w) CPU tensors.
 
 Differences from the reference:
 
@@ -42,6 +44,12 @@ class Trainer:
         self.current_epoch = start_epoch
         self.device = my_pyr.device
         self.l1 = torch.nn.L1Loss()
+        self.lpips_weight = float(getattr(args, "lpips_weight", 0) or 0)
+        self.lpips = None
+        if self.lpips_weight != 0:
+            from ..evaluation.lpips import LPIPS
+            self.lpips = LPIPS(getattr(args, "vgg_weights", None), getattr(args, "lpips_weights", None),
+                               reduction="mean").to(self.device).eval()
 
         self.fusion_net = fusion_net
         self.phase_net = phase_net
@@ -89,6 +97,8 @@ class Trainer:
 
             prediction = torch.clip(prediction, 0, 1).reshape(target.shape).float()
             loss = self.l1(target.float(), prediction)
+            if self.lpips is not None:
+                loss = loss + self.lpips_weight * self.lpips(prediction, target.float())
 
             self.optimizer.zero_grad()
             loss.backward()

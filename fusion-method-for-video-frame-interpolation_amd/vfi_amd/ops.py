@@ -564,6 +564,65 @@ def mse_backward(a, b, upstream, need_a=True, need_b=False):
     return ga, gb
 
 
+# ---- LPIPS -----------------------------------------------------------------------------------
+def _map_ptr(t, name):
+    """(address, batch stride, N, C, HW) of a feature map (N, C, H, W) or (N, C, HW) whose per-sample block is dense"""
+    if isinstance(t, torch.Tensor) and t.dim() == 3:
+        t = t.unsqueeze(-1)
+    p, s = _slice_ptr(t, name)
+    return p, s, t.shape[0], t.shape[1], t.shape[2] * t.shape[3]
+
+
+def _vec(t, count, name):
+    if t is not None and t.numel() != count:
+        raise VfiLibraryError(f"{name} must hold {count} floats, got {tuple(t.shape)}")
+    return _lib.dptr(t, name)
+
+
+def lpips_head_forward(x, y, w, prior=None):
+    """-> (N,) = prior + mean_p sum_c w_c (xh_c - yh_c)^2 of one tap, xh = x / (|x|_channels + 1e-10); x, y may be the two
+    halves of one tensor."""
+    xp, xs, n, c, hw = _map_ptr(x, "x")
+    yp, ys = _map_ptr(y, "y")[:2]
+    if tuple(x.shape) != tuple(y.shape):
+        raise VfiLibraryError("lpips_head_forward: shape mismatch")
+    out = new((n,), x)
+    _lib.call("vfi_lpips_head_forward", xp, xs, yp, ys, _vec(w, c, "w"), _vec(prior, n, "prior"), out.data_ptr(),
+              _reduce_workspace(x).data_ptr(), n, c, hw, _lib.stream_ptr(), work=_prof("byte", 8.0 * n * c * hw, "lpips_head_forward"))
+    return out
+
+
+def lpips_head_backward(x, y, w, upstream, above=None, relu_mask=True, out=None):
+    """-> (above + upstream[n] * d head / dx) * [x > 0 when relu_mask], of x's shape; `out` may be `above` (in place)."""
+    xp, xs, n, c, hw = _map_ptr(x, "x")
+    yp, ys = _map_ptr(y, "y")[:2]
+    if tuple(x.shape) != tuple(y.shape) or (above is not None and tuple(above.shape) != tuple(x.shape)):
+        raise VfiLibraryError("lpips_head_backward: shape mismatch")
+    if out is None:
+        out = new(tuple(x.shape), x)
+    elif tuple(out.shape) != tuple(x.shape):
+        raise VfiLibraryError("lpips_head_backward: out shape mismatch")
+    ap, as_ = (None, 0) if above is None else _map_ptr(above, "above")[:2]
+    op, os_ = _map_ptr(out, "out")[:2]
+    _lib.call("vfi_lpips_head_backward", xp, xs, yp, ys, _vec(w, c, "w"), _vec(upstream, n, "upstream"), ap, as_, op, os_, n, c,
+              hw, int(bool(relu_mask)), _lib.stream_ptr(),
+              work=_prof("byte", 4.0 * n * c * hw * (3 + (above is not None)), "lpips_head_backward"))
+    return out
+
+
+def lpips_normalize(x, adjoint=False, out=None):
+    """(x - mean_c) / std_c of (N, 3, H, W) images in [0, 1] (ImageNet statistics); adjoint: x / std_c."""
+    if x.dim() != 4 or x.shape[1] != 3:
+        raise VfiLibraryError(f"lpips_normalize: (N, 3, H, W) expected, got {tuple(x.shape)}")
+    if out is None:
+        out = new(tuple(x.shape), x)
+    xp, xs = _slice_ptr(x, "x")
+    op, os_ = _slice_ptr(out, "out")
+    _lib.call("vfi_lpips_normalize", xp, xs, op, os_, x.shape[0], x.shape[2] * x.shape[3], int(bool(adjoint)), _lib.stream_ptr(),
+              work=_prof("byte", 8.0 * x.numel(), "lpips_normalize"))
+    return out
+
+
 # ---- glue of a PhaseNet level's backward (DESIGN.md section 14) -----------------------------------------------------
 def resize_bilinear_adjoint(grad, size, out=None):
     """Adjoint of resize_bilinear(x, grad's size, align_corners=False) for x of spatial `size` (any sizes; gather form)."""

@@ -817,6 +817,33 @@ int vfi_triplet_batch_prepare(const unsigned char *src, const int *params, float
                               long long rgb_batch_stride, float *lab, long long lab_slot_stride, long long lab_batch_stride,
                               int B, int Hs, int Ws, int h, int w, vfi_stream_t stream);
 
+/* ------------------------------------------------------------------------------------
+ * LPIPS (piq.LPIPS, reference src/evaluation/evaluate_image.py:22): the head on one tap of the VGG16 trunk, its adjoint,
+ * and the input normalisation.  DESIGN.md section 24.  Same rules as the training paths above: no float atomics, one
+ * writer per element, an order of summation fixed by C and HW alone -- the bits of image n's value depend neither on N
+ * nor on n.
+ * ---------------------------------------------------------------------------------- */
+
+/* out[n] = (prior ? prior[n] : 0) + 1 / HW * sum_p sum_c w[c] (xh_c - yh_c)^2 with xh_c = x_c / (sqrt(sum_k x_k^2) + 1e-10)
+ * at every pixel, yh likewise.  x, y (N, C, HW) fp32 with a batch stride each, any 4-byte alignment (they may be the two
+ * halves of one tensor); w: C floats; prior, out: N floats (out may be prior).  `workspace`: VFI_REDUCE_WORKSPACE_FLOATS.
+ * x == y gives exactly 0. */
+int vfi_lpips_head_forward(const float *x, long long x_bstride, const float *y, long long y_bstride, const float *w,
+                           const float *prior, float *out, float *workspace, int N, int C, int HW, vfi_stream_t stream);
+
+/* grad_x = (above + upstream[n] * d(head value of image n) / dx) * [x > 0 when relu_mask], in one pass; no gradient for y
+ * or w.  With s = |x| + 1e-10, t = |y| + 1e-10, e_c = 2 w_c (x_c / s - y_c / t):
+ *   d/dx_c = 1 / HW * (e_c / s - (sum_k e_k x_k) x_c / (|x| s^2)),   and 0 at a pixel with |x| = 0.
+ * above (optional, NULL = 0): the gradient arriving at x from the layers above, added exactly; grad_x may be `above`. */
+int vfi_lpips_head_backward(const float *x, long long x_bstride, const float *y, long long y_bstride, const float *w,
+                            const float *upstream, const float *above, long long above_bstride, float *grad_x,
+                            long long gx_bstride, int N, int C, int HW, int relu_mask, vfi_stream_t stream);
+
+/* out = (x - mean_c) / std_c per channel of (N, 3, HW) images in [0, 1], mean = (0.485, 0.456, 0.406),
+ * std = (0.229, 0.224, 0.225); adjoint != 0: out = x / std_c, the gradient's way back.  In place allowed. */
+int vfi_lpips_normalize(const float *x, long long x_bstride, float *out, long long out_bstride, int N, int HW, int adjoint,
+                        vfi_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
