@@ -29,8 +29,9 @@ def _sums(a, b):
 
 
 def psnr(x, y, data_range=1.0):
+    """piq.psnr: both images are divided by data_range before the mean, so the 1e-8 guards the scaled error."""
     s1, s2 = _sums(x, y)
-    return 10.0 * math.log10(data_range ** 2 / (s2 / x.numel() + 1e-8))
+    return 10.0 * math.log10(1.0 / (s2 / x.numel() / data_range ** 2 + 1e-8))
 
 
 def ssim(x, y, kernel_size=11, kernel_sigma=1.5, k1=0.01, k2=0.03, downsample=True):
