@@ -116,6 +116,9 @@ SIGNATURES = {
     "vfi_lpips_head_forward": [c_f, c_l, c_f, c_l] + [c_f] * 4 + [c_i] * 3 + [c_s],
     "vfi_lpips_head_backward": [c_f, c_l, c_f, c_l, c_f, c_f, c_f, c_l, c_f, c_l] + [c_i] * 4 + [c_s],
     "vfi_lpips_normalize": [c_f, c_l, c_f, c_l, c_i, c_i, c_i, c_s],
+    "vfi_ssim_loss_forward": [c_f, c_l, c_f, c_l, c_f, c_f] + [c_i] * 5 + [c_fl] * 3 + [c_s],
+    "vfi_ssim_loss_backward": [c_f, c_l, c_f, c_l, c_f, c_f, c_l] + [c_i] * 5 + [c_fl] * 3 + [c_s],
+    "vfi_avg_pool_backward": [c_f, c_f, c_i, c_i, c_i, c_i, c_s],
 }
 REDUCE_WORKSPACE_FLOATS = 4096      # VFI_REDUCE_WORKSPACE_FLOATS
 PHASENET_HEAD_WORKSPACE_FLOATS = 1024 * 520     # VFI_PHASENET_HEAD_WORKSPACE_FLOATS

@@ -17,6 +17,8 @@ Differences from the reference:
 * The type `LPIPS` (not in the reference's grammar, e.g. `1*Charb+0.1*LPIPS`) is the mean over the batch of
   `vfi_amd.evaluation.lpips.LPIPS`, with `args.vgg_weights` as above and its head weights from `args.lpips_weights`,
   default `VFI_LPIPS_WEIGHTS`.  It is matched before the `VGG` substring test.
+* The type `SSIM` (not in the reference's grammar either, e.g. `1*Charb+0.1*SSIM`) is
+  `vfi_amd.evaluation.ssim.SSIMLoss(reduction='mean')`: the mean over the batch of 1 - SSIM, piq's defaults, no weights file.
 * A type containing `GAN` raises NotImplementedError: the discriminators (losses/discriminator.py, adversarial.py) are not
   built.  Any other unknown type raises ValueError; the reference fails there on an unbound name.
 * The modules move to `cuda:<args.gpu_id>` (the reference: 'cuda', after `set_device(gpu_id)`), and stay where they are when
@@ -100,6 +102,9 @@ class Loss(nn.modules.loss._Loss):
                 loss_function = LPIPS(getattr(args, 'vgg_weights', None) or os.environ.get(VGG_WEIGHTS_ENV),
                                       getattr(args, 'lpips_weights', None) or os.environ.get(LPIPS_WEIGHTS_ENV),
                                       reduction='mean')
+            elif loss_type == 'SSIM':
+                from ...evaluation.ssim import SSIMLoss
+                loss_function = SSIMLoss(reduction='mean')
             elif loss_type.find('VGG') >= 0:
                 from .vgg import VGG
                 loss_function = VGG(weights=getattr(args, 'vgg_weights', None) or os.environ.get(VGG_WEIGHTS_ENV))

@@ -4,7 +4,8 @@
 The reference's flags and defaults, plus `--out_dir` (default: the reference's `./output_fusion_net_3_no_uncertainty_map`),
 `--crop H W` (256 256), `--height` (12), `--workers`, `--phasenet_checkpoint`, `--adacof_checkpoint` (defaults: the
 reference's paths), `--test_paths A B C`, and `--lpips_weight` (0) with `--vgg_weights` / `--lpips_weights` (defaults: the
-environment variables VFI_VGG16_WEIGHTS / VFI_LPIPS_WEIGHTS) for the perceptual term of trainer.py.  `--save` is accepted and raises NotImplementedError (trainer.py).
+environment variables VFI_VGG16_WEIGHTS / VFI_LPIPS_WEIGHTS) for the perceptual term of trainer.py, and `--ssim_weight` (0) for
+its structural term (evaluation/ssim.py; no weights file).  `--save` is accepted and raises NotImplementedError (trainer.py).
 
 The network is `FusionNet(kernel, pad, dil)` with its default three uncertainty maps, which `Trainer.predict` feeds it; the
 reference's script builds `FusionNet(uncertainty_maps=0)` (train.py:79), whose first convolution has three input channels
@@ -65,6 +66,9 @@ parser.add_argument('--vgg_weights', type=str, default=os.environ.get('VFI_VGG16
                     help='torchvision vgg16 state dict (default: $VFI_VGG16_WEIGHTS)')
 parser.add_argument('--lpips_weights', type=str, default=os.environ.get('VFI_LPIPS_WEIGHTS'),
                     help='LPIPS head weights (default: $VFI_LPIPS_WEIGHTS)')
+
+# Structural term: loss += ssim_weight * mean (1 - SSIM(clip(prediction), target)); needs no weights file
+parser.add_argument('--ssim_weight', type=float, default=0.0, help='weight of the SSIM term (0: none)')
 
 
 def main(argv=None):

@@ -5,7 +5,9 @@
 `train_batch.fusion_net_inputs`, which is the reference's `predict` up to the call of the network.  The loss is
 `l1(target_rgb, clip(final, 0, 1))` (trainer.py:246-254), plus `args.lpips_weight * mean LPIPS(clip(final, 0, 1), target_rgb)`
 when that weight is not 0 (evaluation/lpips.py, built from `args.vgg_weights` and `args.lpips_weights`; the reference imports
-LPIPS at trainer.py:13 and trains with L1 alone); at 0 nothing is built and the step is the reference's.  `train_loader`
+LPIPS at trainer.py:13 and trains with L1 alone); at 0 nothing is built and the step is the reference's.  Likewise
+`args.ssim_weight * SSIMLoss(clip(final, 0, 1), target_rgb)` (evaluation/ssim.py: the mean of 1 - SSIM over the batch; piq's
+SSIMLoss is imported on the same line of the reference), added after the LPIPS term; at 0 nothing is built.  `train_loader`
 yields `datareader.TripletBatch`es, or the reference's triples of (B, 3, h, w) CPU tensors.
 
 Differences from the reference:
@@ -50,6 +52,11 @@ class Trainer:
             from ..evaluation.lpips import LPIPS
             self.lpips = LPIPS(getattr(args, "vgg_weights", None), getattr(args, "lpips_weights", None),
                                reduction="mean").to(self.device).eval()
+        self.ssim_weight = float(getattr(args, "ssim_weight", 0) or 0)
+        self.ssim = None
+        if self.ssim_weight != 0:
+            from ..evaluation.ssim import SSIMLoss
+            self.ssim = SSIMLoss(reduction="mean")
 
         self.fusion_net = fusion_net
         self.phase_net = phase_net
@@ -99,6 +106,8 @@ class Trainer:
             loss = self.l1(target.float(), prediction)
             if self.lpips is not None:
                 loss = loss + self.lpips_weight * self.lpips(prediction, target.float())
+            if self.ssim is not None:
+                loss = loss + self.ssim_weight * self.ssim(prediction, target.float())
 
             self.optimizer.zero_grad()
             loss.backward()

@@ -623,6 +623,60 @@ def lpips_normalize(x, adjoint=False, out=None):
     return out
 
 
+# ---- SSIM as a loss --------------------------------------------------------------------------
+def ssim_loss_forward(x, y, kernel_size=11, sigma=1.5, c1=0.01 ** 2, c2=0.03 ** 2):
+    """-> (N,) = 1 - mean SSIM of (N, C, H, W) images, one pass; x, y may be the two halves of one tensor."""
+    xp, xs = _slice_ptr(x, "x")
+    yp, ys = _slice_ptr(y, "y")
+    if tuple(x.shape) != tuple(y.shape):
+        raise VfiLibraryError("ssim_loss_forward: shape mismatch")
+    n, c, h, w = x.shape
+    out = new((n,), x)
+    _lib.call("vfi_ssim_loss_forward", xp, xs, yp, ys, out.data_ptr(), _reduce_workspace(x).data_ptr(), n, c, h, w,
+              int(kernel_size), float(sigma), float(c1), float(c2), _lib.stream_ptr(),
+              work=_prof("byte", 8.0 * n * c * h * w, "ssim_loss_forward"))
+    return out
+
+
+def ssim_loss_backward(x, y, upstream, kernel_size=11, sigma=1.5, c1=0.01 ** 2, c2=0.03 ** 2, out=None):
+    """-> upstream[n] * d ssim_loss_forward(x, y)[n] / dx, of x's shape; for y's gradient exchange x and y."""
+    xp, xs = _slice_ptr(x, "x")
+    yp, ys = _slice_ptr(y, "y")
+    if tuple(x.shape) != tuple(y.shape):
+        raise VfiLibraryError("ssim_loss_backward: shape mismatch")
+    n, c, h, w = x.shape
+    if out is None:
+        out = new(tuple(x.shape), x)
+    elif tuple(out.shape) != tuple(x.shape):
+        raise VfiLibraryError("ssim_loss_backward: out shape mismatch")
+    op, os_ = _slice_ptr(out, "out")
+    _lib.call("vfi_ssim_loss_backward", xp, xs, yp, ys, _vec(upstream, n, "upstream"), op, os_, n, c, h, w, int(kernel_size),
+              float(sigma), float(c1), float(c2), _lib.stream_ptr(),
+              work=_prof("byte", 12.0 * n * c * h * w, "ssim_loss_backward"))
+    return out
+
+
+def avg_pool(x, f):
+    """F.avg_pool2d(kernel_size=f) of a dense (N, C, H, W) tensor (floor)."""
+    n, c, h, w = x.shape
+    out = new((n, c, h // f, w // f), x)
+    _lib.call("vfi_avg_pool", _lib.dptr(x, "x"), out.data_ptr(), n * c, h, w, int(f), _lib.stream_ptr(),
+              work=_prof("byte", 4.0 * (x.numel() + out.numel()), "avg_pool"))
+    return out
+
+
+def avg_pool_backward(grad, size, f):
+    """Adjoint of avg_pool for an input of spatial `size`: grad / f^2 over each window, 0 where the floor dropped pixels."""
+    n, c, ho, wo = grad.shape
+    h, w = size
+    if (ho, wo) != (h // f, w // f):
+        raise VfiLibraryError(f"avg_pool_backward: grad {tuple(grad.shape)} is not ({h}, {w}) pooled by {f}")
+    out = new((n, c, h, w), grad)
+    _lib.call("vfi_avg_pool_backward", _lib.dptr(grad, "grad"), out.data_ptr(), n * c, h, w, int(f), _lib.stream_ptr(),
+              work=_prof("byte", 4.0 * (grad.numel() + out.numel()), "avg_pool_backward"))
+    return out
+
+
 # ---- glue of a PhaseNet level's backward (DESIGN.md section 14) -----------------------------------------------------
 def resize_bilinear_adjoint(grad, size, out=None):
     """Adjoint of resize_bilinear(x, grad's size, align_corners=False) for x of spatial `size` (any sizes; gather form)."""

@@ -844,6 +844,37 @@ int vfi_lpips_head_backward(const float *x, long long x_bstride, const float *y,
 int vfi_lpips_normalize(const float *x, long long x_bstride, float *out, long long out_bstride, int N, int HW, int adjoint,
                         vfi_stream_t stream);
 
+/* ------------------------------------------------------------------------------------
+ * SSIM as a loss (piq.SSIMLoss, imported at reference src/fusion_net/trainer.py:13).  DESIGN.md section 26.  The rules of
+ * the training paths: no float atomics, one writer per element, an order of summation fixed by (C, H, W) alone -- the
+ * bits of image n's value and gradient depend neither on N nor on n.
+ *   taps g[i] ~ exp(-(i - r)^2 / (2 sigma^2)), r = kernel_size / 2, normalised (made on the host in double, rounded once)
+ *   mu_x = G*x, mu_y = G*y, Exx = G*x^2, Eyy = G*y^2, Exy = G*xy, separable, valid region (H - 2r) x (W - 2r) only
+ *   sxx = Exx - mu_x^2, syy = Eyy - mu_y^2, sxy = Exy - mu_x mu_y
+ *   ssim = (2 mu_x mu_y + c1) / (mu_x^2 + mu_y^2 + c1) * (2 sxy + c2) / (sxx + syy + c2)
+ * x, y: (N, C, H, W) fp32 with a batch stride each, any 4-byte alignment (they may be the two halves of one tensor).
+ * kernel_size odd, 3 ... 11, sigma > 0, N, C >= 1, else VFI_ERR_INVALID_ARG; H or W below kernel_size is VFI_ERR_SHAPE;
+ * nothing is written in either case.
+ * ---------------------------------------------------------------------------------- */
+
+/* out[n] = 1 - mean of ssim over C * (H - 2r) * (W - 2r), in one pass over x and y (the moments stay on the CU).
+ * `workspace`: VFI_REDUCE_WORKSPACE_FLOATS.  x == y gives exactly 0. */
+int vfi_ssim_loss_forward(const float *x, long long x_bstride, const float *y, long long y_bstride, float *out,
+                          float *workspace, int N, int C, int H, int W, int kernel_size, float sigma, float c1, float c2,
+                          vfi_stream_t stream);
+
+/* grad_x = upstream[n] * d out[n] / dx, gather form; x and y are all it reads.  No gradient for y: SSIM is symmetric, call
+ * with x and y exchanged.  With count = C (H - 2r) (W - 2r), l and cs the two factors above, D1 and D2 their denominators,
+ *   B = -l cs / D2,  Cm = 2 l / D2,  A = cs (2 mu_y / D1 - 2 mu_x l / D1) - 2 mu_x B - mu_y Cm   (0 outside the valid region)
+ *   grad_x(q) = -upstream[n] / count * ((G (*) A)(q) + 2 x(q) (G (*) B)(q) + y(q) (G (*) Cm)(q)),  (*) the full correlation. */
+int vfi_ssim_loss_backward(const float *x, long long x_bstride, const float *y, long long y_bstride, const float *upstream,
+                           float *grad_x, long long gx_bstride, int N, int C, int H, int W, int kernel_size, float sigma,
+                           float c1, float c2, vfi_stream_t stream);
+
+/* Adjoint of vfi_avg_pool: grad (planes, H/f, W/f) -> grad_x (planes, H, W), dense; every pixel of a window gets grad / f^2,
+ * the rows and columns the floor drops get exactly 0. */
+int vfi_avg_pool_backward(const float *grad, float *grad_x, int planes, int H, int W, int f, vfi_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
