@@ -592,6 +592,9 @@ __global__ void bn_stats_final_kernel(const float *__restrict__ part, int bpc, f
 }
 
 __device__ __forceinline__ float bn_elu(float v) { return __builtin_amdgcn_fmed3f(v, __expf(v) - 1.0f, 0.0f); }   // apply_act's ELU
+// LeakyReLU(slope) of the discriminator's blocks (vfi_bn_leaky_*): a third instantiation of the kernels below, internal to
+// this file -- not a vfi_act value, the public entries vfi_bn_act_* keep refusing everything but none and ELU
+constexpr int kActLeaky = 100;
 
 // out = act(scale (y - mean) + beta), scale = gamma / sqrt(var + eps) formed once per block.  (y - mean) first: folded into
 // one shift, a channel with |mean| >> sigma would lose its digits in scale * y + shift.  out may be y itself.
@@ -599,7 +602,7 @@ template <typename T, int ACT>
 __global__ __launch_bounds__(kThreads) void bn_act_forward_kernel(const float *y, long long y_bs, const float *__restrict__ mean,
                                                                   const float *__restrict__ var, const float *__restrict__ gamma,
                                                                   const float *__restrict__ beta, float eps, float *out,
-                                                                  long long o_bs, int C, int HW) {
+                                                                  long long o_bs, int C, int HW, float slope) {
     constexpr int L = sizeof(T) / sizeof(float);
     const int plane = blockIdx.y, n = plane / C, c = plane - n * C;
     const float mu = mean[c], sc = gamma[c] * (1.0f / sqrtf(var[c] + eps)), sh = beta[c];
@@ -611,7 +614,7 @@ __global__ __launch_bounds__(kThreads) void bn_act_forward_kernel(const float *y
 #pragma unroll
         for (int l = 0; l < L; ++l) {
             const float z = fmaf(lane_get(v, l) - mu, sc, sh);
-            lane_set(r, l, ACT == VFI_ACT_ELU ? bn_elu(z) : z);
+            lane_set(r, l, ACT == VFI_ACT_ELU ? bn_elu(z) : ACT == kActLeaky ? (z > 0.0f ? z : z * slope) : z);
         }
         *reinterpret_cast<T *>(op + p) = r;
     }
@@ -621,10 +624,13 @@ struct BnBackArgs {
     const float *g_t, *t, *y, *mean, *var, *gamma;
     long long gt_bs, t_bs, y_bs, gy_bs, chunk;
     float *g_y, *g_gamma, *g_beta, *part;
-    float eps;
+    float eps, slope;
     int N, C, HW, bpc;
 };
-template <int ACT> __device__ __forceinline__ float bn_gz(float g, float t) { return ACT == VFI_ACT_ELU ? (t > 0.0f ? g : g * (t + 1.0f)) : g; }
+// g times the activation's derivative, from the output t (LeakyReLU: its sign, slope > 0)
+template <int ACT> __device__ __forceinline__ float bn_gz(float g, float t, float slope) {
+    return ACT == VFI_ACT_ELU ? (t > 0.0f ? g : g * (t + 1.0f)) : ACT == kActLeaky ? (t > 0.0f ? g : g * slope) : g;
+}
 
 // pass 1, stage 1: block (b, c) writes (sum g_z, sum g_z xhat) of its chunk
 template <typename T, int ACT>
@@ -641,11 +647,11 @@ __global__ __launch_bounds__(kThreads) void bn_back_partial_kernel(BnBackArgs a)
         const T g = *reinterpret_cast<const T *>(a.g_t + (size_t)n * a.gt_bs + co + p);
         const T yv = *reinterpret_cast<const T *>(a.y + (size_t)n * a.y_bs + co + p);
         T tv = g;
-        if (ACT == VFI_ACT_ELU) tv = *reinterpret_cast<const T *>(a.t + (size_t)n * a.t_bs + co + p);
+        if (ACT != VFI_ACT_NONE) tv = *reinterpret_cast<const T *>(a.t + (size_t)n * a.t_bs + co + p);
         float s0 = 0.0f, s1 = 0.0f;
 #pragma unroll
         for (int l = 0; l < L; ++l) {
-            const float gz = bn_gz<ACT>(lane_get(g, l), lane_get(tv, l));
+            const float gz = bn_gz<ACT>(lane_get(g, l), lane_get(tv, l), a.slope);
             s0 += gz;
             s1 = fmaf(gz, (lane_get(yv, l) - mu) * inv, s1);
         }
@@ -678,15 +684,15 @@ __global__ __launch_bounds__(kThreads) void bn_back_data_kernel(BnBackArgs a) {
     const float mb = a.g_beta[c] / cnt, mg = a.g_gamma[c] / cnt;
     const size_t co = (size_t)c * a.HW;
     const float *gp = a.g_t + (size_t)n * a.gt_bs + co, *yp = a.y + (size_t)n * a.y_bs + co;
-    const float *tp = ACT == VFI_ACT_ELU ? a.t + (size_t)n * a.t_bs + co : gp;
+    const float *tp = ACT != VFI_ACT_NONE ? a.t + (size_t)n * a.t_bs + co : gp;
     float *op = a.g_y + (size_t)n * a.gy_bs + co;
     for (int p = (blockIdx.x * kThreads + threadIdx.x) * L; p < a.HW; p += gridDim.x * kThreads * L) {
         const T g = *reinterpret_cast<const T *>(gp + p), yv = *reinterpret_cast<const T *>(yp + p);
         T tv = g, r;
-        if (ACT == VFI_ACT_ELU) tv = *reinterpret_cast<const T *>(tp + p);
+        if (ACT != VFI_ACT_NONE) tv = *reinterpret_cast<const T *>(tp + p);
 #pragma unroll
         for (int l = 0; l < L; ++l) {
-            const float gz = bn_gz<ACT>(lane_get(g, l), lane_get(tv, l));
+            const float gz = bn_gz<ACT>(lane_get(g, l), lane_get(tv, l), a.slope);
             const float xh = (lane_get(yv, l) - mu) * inv;
             lane_set(r, l, k * ((gz - mb) - xh * mg));
         }
@@ -899,22 +905,79 @@ extern "C" int vfi_bn_stats(const float *y, long long y_bstride, int N, int C, i
     return vfi::check_launch("vfi_bn_stats");
 }
 
+// act: VFI_ACT_NONE, VFI_ACT_ELU or kActLeaky (slope read by the last alone); `what` names the public entry in messages
+static int bn_forward(const char *what, const float *y, long long y_bstride, const float *mean, const float *var, const float *gamma,
+                      const float *beta, float eps, int act, float slope, float *out, long long out_bstride, int N, int C, int HW,
+                      vfi_stream_t stream) {
+    VFI_REQUIRE(y && mean && var && gamma && beta && out, VFI_ERR_INVALID_ARG, "%s: null pointer", what);
+    VFI_REQUIRE(N > 0 && C > 0 && HW > 0 && eps >= 0.0f, VFI_ERR_INVALID_ARG, "%s: bad sizes", what);
+    VFI_REQUIRE((long long)N * C <= 65535 && HW < (1 << 30), VFI_ERR_UNSUPPORTED, "%s: N * C = %lld planes, HW = %d beyond the grid", what, (long long)N * C, HW);
+    const bool v4 = HW % 4 == 0 && y_bstride % 4 == 0 && out_bstride % 4 == 0 && aligned16(y) && aligned16(out);
+    hipStream_t s = vfi::as_stream(stream);
+    const dim3 grid = bn_plane_grid(N, C, HW, v4 ? 4 : 1);
+#define VFI_BN_FWD(T, ACT) \
+    hipLaunchKernelGGL((bn_act_forward_kernel<T, ACT>), grid, dim3(kThreads), 0, s, y, y_bstride, mean, var, gamma, beta, eps, out, out_bstride, C, HW, slope)
+    if (act == VFI_ACT_ELU) { if (v4) VFI_BN_FWD(float4, VFI_ACT_ELU); else VFI_BN_FWD(float, VFI_ACT_ELU); }
+    else if (act == kActLeaky) { if (v4) VFI_BN_FWD(float4, kActLeaky); else VFI_BN_FWD(float, kActLeaky); }
+    else { if (v4) VFI_BN_FWD(float4, VFI_ACT_NONE); else VFI_BN_FWD(float, VFI_ACT_NONE); }
+#undef VFI_BN_FWD
+    return vfi::check_launch(what);
+}
+
 extern "C" int vfi_bn_act_forward(const float *y, long long y_bstride, const float *mean, const float *var, const float *gamma,
                                   const float *beta, float eps, int act, float *out, long long out_bstride, int N, int C, int HW,
                                   vfi_stream_t stream) {
     VFI_REQUIRE(y && mean && var && gamma && beta && out, VFI_ERR_INVALID_ARG, "vfi_bn_act_forward: null pointer");
     VFI_REQUIRE(N > 0 && C > 0 && HW > 0 && eps >= 0.0f, VFI_ERR_INVALID_ARG, "vfi_bn_act_forward: bad sizes");
     VFI_REQUIRE(act == VFI_ACT_NONE || act == VFI_ACT_ELU, VFI_ERR_UNSUPPORTED, "vfi_bn_act_forward: act %d (none and ELU only)", act);
-    VFI_REQUIRE((long long)N * C <= 65535 && HW < (1 << 30), VFI_ERR_UNSUPPORTED, "vfi_bn_act_forward: N * C = %lld planes, HW = %d beyond the grid", (long long)N * C, HW);
-    const bool v4 = HW % 4 == 0 && y_bstride % 4 == 0 && out_bstride % 4 == 0 && aligned16(y) && aligned16(out);
+    return bn_forward("vfi_bn_act_forward", y, y_bstride, mean, var, gamma, beta, eps, act, 1.0f, out, out_bstride, N, C, HW, stream);
+}
+
+extern "C" int vfi_bn_leaky_forward(const float *y, long long y_bstride, const float *mean, const float *var, const float *gamma,
+                                    const float *beta, float eps, float slope, float *out, long long out_bstride, int N, int C,
+                                    int HW, vfi_stream_t stream) {
+    VFI_REQUIRE(slope > 0.0f, VFI_ERR_INVALID_ARG, "vfi_bn_leaky_forward: slope %g (must be positive)", (double)slope);
+    return bn_forward("vfi_bn_leaky_forward", y, y_bstride, mean, var, gamma, beta, eps, kActLeaky, slope, out, out_bstride, N, C, HW,
+                      stream);
+}
+
+static int bn_backward(const char *what, const float *g_t, long long gt_bstride, const float *t, long long t_bstride, const float *y,
+                       long long y_bstride, const float *mean, const float *var, const float *gamma, float eps, int act, float slope,
+                       float *g_y, long long gy_bstride, float *g_gamma, float *g_beta, float *workspace, int N, int C, int HW,
+                       vfi_stream_t stream) {
+    VFI_REQUIRE(g_t && y && mean && var && g_gamma && g_beta && workspace, VFI_ERR_INVALID_ARG, "%s: null pointer", what);
+    VFI_REQUIRE(act == VFI_ACT_NONE || t, VFI_ERR_INVALID_ARG, "%s: the activation needs its output t", what);
+    VFI_REQUIRE(!g_y || gamma, VFI_ERR_INVALID_ARG, "%s: g_y needs gamma", what);
+    VFI_REQUIRE(N > 0 && C > 0 && HW > 0 && eps >= 0.0f, VFI_ERR_INVALID_ARG, "%s: bad sizes", what);
+    VFI_REQUIRE(C <= 65535 && 3ll * C <= VFI_REDUCE_WORKSPACE_FLOATS && (long long)N * C <= 65535 && HW < (1 << 30) && (long long)N * HW < (1ll << 40) &&
+                (long long)C * HW < (1ll << 40), VFI_ERR_UNSUPPORTED, "%s: N = %d, C = %d, HW = %d beyond the workspace or the grid", what, N, C, HW);
+    const BnCut cut = bn_cut(N, C, HW);
+    BnBackArgs a{};
+    a.g_t = g_t; a.t = t; a.y = y; a.mean = mean; a.var = var; a.gamma = gamma; a.gt_bs = gt_bstride; a.t_bs = t_bstride;
+    a.y_bs = y_bstride; a.gy_bs = gy_bstride; a.chunk = cut.chunk; a.g_y = g_y; a.g_gamma = g_gamma; a.g_beta = g_beta;
+    a.part = workspace; a.eps = eps; a.slope = slope; a.N = N; a.C = C; a.HW = HW; a.bpc = cut.bpc;
+    const bool elu = act == VFI_ACT_ELU, leaky = act == kActLeaky;
+    const bool v4 = HW % 4 == 0 && gt_bstride % 4 == 0 && y_bstride % 4 == 0 && aligned16(g_t) && aligned16(y) &&
+                    (!(elu || leaky) || (t_bstride % 4 == 0 && aligned16(t))) && (!g_y || (gy_bstride % 4 == 0 && aligned16(g_y)));
     hipStream_t s = vfi::as_stream(stream);
-    const dim3 grid = bn_plane_grid(N, C, HW, v4 ? 4 : 1);
-#define VFI_BN_FWD(T, ACT) \
-    hipLaunchKernelGGL((bn_act_forward_kernel<T, ACT>), grid, dim3(kThreads), 0, s, y, y_bstride, mean, var, gamma, beta, eps, out, out_bstride, C, HW)
-    if (act == VFI_ACT_ELU) { if (v4) VFI_BN_FWD(float4, VFI_ACT_ELU); else VFI_BN_FWD(float, VFI_ACT_ELU); }
-    else { if (v4) VFI_BN_FWD(float4, VFI_ACT_NONE); else VFI_BN_FWD(float, VFI_ACT_NONE); }
-#undef VFI_BN_FWD
-    return vfi::check_launch("vfi_bn_act_forward");
+    const dim3 rgrid(cut.bpc, C);
+    if (elu) { if (v4) hipLaunchKernelGGL((bn_back_partial_kernel<float4, VFI_ACT_ELU>), rgrid, dim3(kThreads), 0, s, a);
+               else hipLaunchKernelGGL((bn_back_partial_kernel<float, VFI_ACT_ELU>), rgrid, dim3(kThreads), 0, s, a); }
+    else if (leaky) { if (v4) hipLaunchKernelGGL((bn_back_partial_kernel<float4, kActLeaky>), rgrid, dim3(kThreads), 0, s, a);
+                      else hipLaunchKernelGGL((bn_back_partial_kernel<float, kActLeaky>), rgrid, dim3(kThreads), 0, s, a); }
+    else { if (v4) hipLaunchKernelGGL((bn_back_partial_kernel<float4, VFI_ACT_NONE>), rgrid, dim3(kThreads), 0, s, a);
+           else hipLaunchKernelGGL((bn_back_partial_kernel<float, VFI_ACT_NONE>), rgrid, dim3(kThreads), 0, s, a); }
+    hipLaunchKernelGGL(bn_back_final_kernel, dim3(C), dim3(64), 0, s, workspace, cut.bpc, g_gamma, g_beta);
+    if (g_y) {
+        const dim3 grid = bn_plane_grid(N, C, HW, v4 ? 4 : 1);
+        if (elu) { if (v4) hipLaunchKernelGGL((bn_back_data_kernel<float4, VFI_ACT_ELU>), grid, dim3(kThreads), 0, s, a);
+                   else hipLaunchKernelGGL((bn_back_data_kernel<float, VFI_ACT_ELU>), grid, dim3(kThreads), 0, s, a); }
+        else if (leaky) { if (v4) hipLaunchKernelGGL((bn_back_data_kernel<float4, kActLeaky>), grid, dim3(kThreads), 0, s, a);
+                          else hipLaunchKernelGGL((bn_back_data_kernel<float, kActLeaky>), grid, dim3(kThreads), 0, s, a); }
+        else { if (v4) hipLaunchKernelGGL((bn_back_data_kernel<float4, VFI_ACT_NONE>), grid, dim3(kThreads), 0, s, a);
+               else hipLaunchKernelGGL((bn_back_data_kernel<float, VFI_ACT_NONE>), grid, dim3(kThreads), 0, s, a); }
+    }
+    return vfi::check_launch(what);
 }
 
 extern "C" int vfi_bn_act_backward(const float *g_t, long long gt_bstride, const float *t, long long t_bstride, const float *y,
@@ -923,32 +986,15 @@ extern "C" int vfi_bn_act_backward(const float *g_t, long long gt_bstride, const
                                    int HW, vfi_stream_t stream) {
     VFI_REQUIRE(g_t && y && mean && var && g_gamma && g_beta && workspace, VFI_ERR_INVALID_ARG, "vfi_bn_act_backward: null pointer");
     VFI_REQUIRE(act == VFI_ACT_NONE || act == VFI_ACT_ELU, VFI_ERR_UNSUPPORTED, "vfi_bn_act_backward: act %d (none and ELU only)", act);
-    VFI_REQUIRE(act == VFI_ACT_NONE || t, VFI_ERR_INVALID_ARG, "vfi_bn_act_backward: ELU needs its output t");
-    VFI_REQUIRE(!g_y || gamma, VFI_ERR_INVALID_ARG, "vfi_bn_act_backward: g_y needs gamma");
-    VFI_REQUIRE(N > 0 && C > 0 && HW > 0 && eps >= 0.0f, VFI_ERR_INVALID_ARG, "vfi_bn_act_backward: bad sizes");
-    VFI_REQUIRE(C <= 65535 && 3ll * C <= VFI_REDUCE_WORKSPACE_FLOATS && (long long)N * C <= 65535 && HW < (1 << 30) && (long long)N * HW < (1ll << 40) &&
-                (long long)C * HW < (1ll << 40), VFI_ERR_UNSUPPORTED, "vfi_bn_act_backward: N = %d, C = %d, HW = %d beyond the workspace or the grid", N, C, HW);
-    const BnCut cut = bn_cut(N, C, HW);
-    BnBackArgs a{};
-    a.g_t = g_t; a.t = t; a.y = y; a.mean = mean; a.var = var; a.gamma = gamma; a.gt_bs = gt_bstride; a.t_bs = t_bstride;
-    a.y_bs = y_bstride; a.gy_bs = gy_bstride; a.chunk = cut.chunk; a.g_y = g_y; a.g_gamma = g_gamma; a.g_beta = g_beta;
-    a.part = workspace; a.eps = eps; a.N = N; a.C = C; a.HW = HW; a.bpc = cut.bpc;
-    const bool elu = act == VFI_ACT_ELU;
-    const bool v4 = HW % 4 == 0 && gt_bstride % 4 == 0 && y_bstride % 4 == 0 && aligned16(g_t) && aligned16(y) &&
-                    (!elu || (t_bstride % 4 == 0 && aligned16(t))) && (!g_y || (gy_bstride % 4 == 0 && aligned16(g_y)));
-    hipStream_t s = vfi::as_stream(stream);
-    const dim3 rgrid(cut.bpc, C);
-    if (elu) { if (v4) hipLaunchKernelGGL((bn_back_partial_kernel<float4, VFI_ACT_ELU>), rgrid, dim3(kThreads), 0, s, a);
-               else hipLaunchKernelGGL((bn_back_partial_kernel<float, VFI_ACT_ELU>), rgrid, dim3(kThreads), 0, s, a); }
-    else { if (v4) hipLaunchKernelGGL((bn_back_partial_kernel<float4, VFI_ACT_NONE>), rgrid, dim3(kThreads), 0, s, a);
-           else hipLaunchKernelGGL((bn_back_partial_kernel<float, VFI_ACT_NONE>), rgrid, dim3(kThreads), 0, s, a); }
-    hipLaunchKernelGGL(bn_back_final_kernel, dim3(C), dim3(64), 0, s, workspace, cut.bpc, g_gamma, g_beta);
-    if (g_y) {
-        const dim3 grid = bn_plane_grid(N, C, HW, v4 ? 4 : 1);
-        if (elu) { if (v4) hipLaunchKernelGGL((bn_back_data_kernel<float4, VFI_ACT_ELU>), grid, dim3(kThreads), 0, s, a);
-                   else hipLaunchKernelGGL((bn_back_data_kernel<float, VFI_ACT_ELU>), grid, dim3(kThreads), 0, s, a); }
-        else { if (v4) hipLaunchKernelGGL((bn_back_data_kernel<float4, VFI_ACT_NONE>), grid, dim3(kThreads), 0, s, a);
-               else hipLaunchKernelGGL((bn_back_data_kernel<float, VFI_ACT_NONE>), grid, dim3(kThreads), 0, s, a); }
-    }
-    return vfi::check_launch("vfi_bn_act_backward");
+    return bn_backward("vfi_bn_act_backward", g_t, gt_bstride, t, t_bstride, y, y_bstride, mean, var, gamma, eps, act, 1.0f, g_y,
+                       gy_bstride, g_gamma, g_beta, workspace, N, C, HW, stream);
+}
+
+extern "C" int vfi_bn_leaky_backward(const float *g_t, long long gt_bstride, const float *t, long long t_bstride, const float *y,
+                                     long long y_bstride, const float *mean, const float *var, const float *gamma, float eps,
+                                     float slope, float *g_y, long long gy_bstride, float *g_gamma, float *g_beta, float *workspace,
+                                     int N, int C, int HW, vfi_stream_t stream) {
+    VFI_REQUIRE(slope > 0.0f, VFI_ERR_INVALID_ARG, "vfi_bn_leaky_backward: slope %g (must be positive)", (double)slope);
+    return bn_backward("vfi_bn_leaky_backward", g_t, gt_bstride, t, t_bstride, y, y_bstride, mean, var, gamma, eps, kActLeaky, slope,
+                       g_y, gy_bstride, g_gamma, g_beta, workspace, N, C, HW, stream);
 }

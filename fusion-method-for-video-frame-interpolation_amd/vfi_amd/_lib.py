@@ -110,6 +110,12 @@ SIGNATURES = {
     "vfi_bn_stats": [c_f, c_l, c_i, c_i, c_i, c_f, c_f, c_f, c_s],
     "vfi_bn_act_forward": [c_f, c_l, c_f, c_f, c_f, c_f, c_fl, c_i, c_f, c_l, c_i, c_i, c_i, c_s],
     "vfi_bn_act_backward": [c_f, c_l] * 3 + [c_f, c_f, c_f, c_fl, c_i, c_f, c_l, c_f, c_f, c_f, c_i, c_i, c_i, c_s],
+    "vfi_bn_leaky_forward": [c_f, c_l, c_f, c_f, c_f, c_f, c_fl, c_fl, c_f, c_l, c_i, c_i, c_i, c_s],
+    "vfi_bn_leaky_backward": [c_f, c_l] * 3 + [c_f, c_f, c_f, c_fl, c_fl, c_f, c_l, c_f, c_f, c_f, c_i, c_i, c_i, c_s],
+    "vfi_phase_split": [c_f, c_l, c_f, c_l] + [c_i] * 4 + [c_s],
+    "vfi_phase_merge": [c_f, c_l, c_f, c_l] + [c_i] * 4 + [c_s],
+    "vfi_linear_forward": [c_f] * 4 + [c_i] * 3 + [c_fl, c_s],
+    "vfi_linear_backward": [c_f] * 3 + [c_fl] + [c_f] * 4 + [c_i] * 3 + [c_s],
     "vfi_l1_forward": [c_f, c_f, c_l, c_i, c_fl, c_f, c_f, c_s],
     "vfi_l1_backward": [c_f] * 5 + [c_l, c_i, c_fl, c_s],
     "vfi_triplet_batch_prepare": [c_f, ctypes.c_void_p, c_f, c_l, c_l, c_f, c_l, c_l] + [c_i] * 5 + [c_s],

@@ -19,8 +19,11 @@ Differences from the reference:
   default `VFI_LPIPS_WEIGHTS`.  It is matched before the `VGG` substring test.
 * The type `SSIM` (not in the reference's grammar either, e.g. `1*Charb+0.1*SSIM`) is
   `vfi_amd.evaluation.ssim.SSIMLoss(reduction='mean')`: the mean over the batch of 1 - SSIM, piq's defaults, no weights file.
-* A type containing `GAN` raises NotImplementedError: the discriminators (losses/discriminator.py, adversarial.py) are not
-  built.  Any other unknown type raises ValueError; the reference fails there on an unbound name.
+* The types `GAN`, `WGAN` and `FI_GAN` build `adversarial.Adversarial(args, type)` (HIP discriminator),
+  and `forward` hands `input_frames` to `FI_GAN`, as the reference does.  The classifier of the discriminator is sized by
+  `args.patch_size`: an `args` without one raises NotImplementedError (the discriminator cannot be sized), and so do, always,
+  `WGAN_GP` (its gradient penalty needs a double backward through every kernel) and `T_WGAN_GP` (the temporal discriminator's
+  Conv3d front end is not built).  Any other unknown type raises ValueError; the reference fails there on an unbound name.
 * The modules move to `cuda:<args.gpu_id>` (the reference: 'cuda', after `set_device(gpu_id)`), and stay where they are when
   there is no device, so the string can be parsed on a host.
 """
@@ -109,8 +112,14 @@ class Loss(nn.modules.loss._Loss):
                 from .vgg import VGG
                 loss_function = VGG(weights=getattr(args, 'vgg_weights', None) or os.environ.get(VGG_WEIGHTS_ENV))
             elif loss_type.find('GAN') >= 0:
-                raise NotImplementedError(f"loss type {loss_type!r}: the adversarial terms need the reference's "
-                                          "discriminator, which is not built")
+                from .adversarial import TYPES, Adversarial
+                if loss_type not in TYPES:
+                    raise NotImplementedError(f"loss type {loss_type!r}: its discriminator is not built (only "
+                                              f"{', '.join(TYPES)}: no gradient penalty, no temporal discriminator)")
+                if getattr(args, 'patch_size', None) is None:
+                    raise NotImplementedError(f"loss type {loss_type!r}: args has no patch_size, which sizes the "
+                                              "discriminator's classifier")
+                loss_function = Adversarial(args, loss_type)
             elif loss_type in REGULARIZERS:
                 self.regularize.append({
                     'type': loss_type,
@@ -141,7 +150,10 @@ class Loss(nn.modules.loss._Loss):
         losses = []
         for l in self.loss:
             if l['function'] is not None:
-                loss = l['function'](output['frame1'], gt)
+                if l['type'] == 'FI_GAN':
+                    loss = l['function'](output['frame1'], gt, input_frames)
+                else:
+                    loss = l['function'](output['frame1'], gt)
                 effective_loss = l['weight'] * loss
                 losses.append(effective_loss)
 

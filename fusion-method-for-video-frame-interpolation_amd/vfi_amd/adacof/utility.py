@@ -4,7 +4,8 @@
 reduction forward, one streaming pass backward) when they are given HIP tensors of which one requires grad, so the
 reference loss `1*Charb` on `output['frame1']` stays off torch's elementwise kernels; any other argument (CPU tensors,
 float64, nothing requiring grad) takes the plain torch expression (`_on_hip` decides, for the MSE / L1 nodes of
-`losses/__init__.py` too).  The trainer's `Loss` and its VGG term are in `losses/`; the GAN terms are not mirrored.
+`losses/__init__.py` too).  The trainer's `Loss`, its VGG term and its GAN terms (`losses/adversarial.py`,
+whose discriminator takes its optimiser and scheduler from `make_optimizer` / `make_scheduler` here) are in `losses/`.
 """
 import torch
 import torch.nn as nn

@@ -863,6 +863,172 @@ def bn_act_backward(g_t, t, y, mean, var, gamma, eps, act="elu", need_data=True,
     return g_y, g_gamma, g_beta
 
 
+# ---- the AdaCoF trainer's discriminator -----------------------------------------------------------
+def bn_leaky_forward(y, mean, var, gamma, beta, eps, slope, out=None):
+    """leaky(gamma (y - mean) / sqrt(var + eps) + beta), leaky(z) = z if z > 0 else slope z (vfi_bn_leaky_forward); y and out
+    may be channel slices, out may be y."""
+    n, c, h, w = y.shape
+    if out is None:
+        out = new((n, c, h, w), y)
+    elif tuple(out.shape) != (n, c, h, w):
+        raise VfiLibraryError(f"bn_leaky_forward: out shape {tuple(out.shape)} != {(n, c, h, w)}")
+    yp, ys = _slice_ptr(y, "y")
+    op, os_ = _slice_ptr(out, "out")
+    _lib.call("vfi_bn_leaky_forward", yp, ys, _channel_vec(mean, c, "mean"), _channel_vec(var, c, "var"),
+              _channel_vec(gamma, c, "gamma"), _channel_vec(beta, c, "beta"), float(eps), float(slope), op, os_, n, c, h * w,
+              _lib.stream_ptr(), work=_prof("byte", 8.0 * n * c * h * w, "bn_leaky_forward"))
+    return out
+
+
+def bn_leaky_backward(g_t, t, y, mean, var, gamma, eps, slope, need_data=True, out=None):
+    """Adjoint of bn_stats + bn_leaky_forward (vfi_bn_leaky_backward) -> (g_y or None, g_gamma (C,), g_beta (C,)); t is the
+    forward's output (its sign gives the LeakyReLU's derivative).  `out`: where g_y goes, g_t itself is fine."""
+    n, c, h, w = g_t.shape
+    if tuple(y.shape) != (n, c, h, w) or tuple(t.shape) != (n, c, h, w):
+        raise VfiLibraryError("bn_leaky_backward: shape mismatch")
+    gp, gs = _slice_ptr(g_t, "g_t")
+    tp, ts = _slice_ptr(t, "t")
+    yp, ys = _slice_ptr(y, "y")
+    g_y = None
+    if need_data:
+        g_y = new((n, c, h, w), g_t) if out is None else out
+        if tuple(g_y.shape) != (n, c, h, w):
+            raise VfiLibraryError(f"bn_leaky_backward: out shape {tuple(g_y.shape)} != {(n, c, h, w)}")
+    op, os_ = (None, 0) if g_y is None else _slice_ptr(g_y, "out")
+    g_gamma, g_beta = new((c,), g_t), new((c,), g_t)
+    _lib.call("vfi_bn_leaky_backward", gp, gs, tp, ts, yp, ys, _channel_vec(mean, c, "mean"), _channel_vec(var, c, "var"),
+              _channel_vec(gamma, c, "gamma"), float(eps), float(slope), op, os_, g_gamma.data_ptr(), g_beta.data_ptr(),
+              _reduce_workspace(g_t).data_ptr(), n, c, h * w, _lib.stream_ptr(),
+              work=_prof("byte", 4.0 * n * c * h * w * (3 * (1 + need_data) + need_data), "bn_leaky_backward"))
+    return g_y, g_gamma, g_beta
+
+
+def phase_split(x, out=None):
+    """xs (N, 4C, ceil(H/2), ceil(W/2)) with xs[n, (2 py + px) C + c, i, j] = x[n, c, 2 i + py, 2 j + px], zero beyond the
+    edge (vfi_phase_split): the tensor whose stride-1 3x3 convolution is x's stride-2 one."""
+    n, c, h, w = x.shape
+    shape = (n, 4 * c, (h + 1) // 2, (w + 1) // 2)
+    if out is None:
+        out = new(shape, x)
+    elif tuple(out.shape) != shape:
+        raise VfiLibraryError(f"phase_split: out shape {tuple(out.shape)} != {shape}")
+    xp, xs = _slice_ptr(x, "x")
+    op, os_ = _slice_ptr(out, "out")
+    _lib.call("vfi_phase_split", xp, xs, op, os_, n, c, h, w, _lib.stream_ptr(),
+              work=_prof("byte", 4.0 * n * c * (h * w + 4 * shape[2] * shape[3]), "phase_split"))
+    return out
+
+
+def phase_merge(gs, size, out=None):
+    """Adjoint of phase_split: (N, C, H, W) = size's (H, W) from gs (N, 4C, ceil(H/2), ceil(W/2)) (vfi_phase_merge)."""
+    n, c4, h2, w2 = gs.shape
+    h, w = size
+    if c4 % 4 or (h + 1) // 2 != h2 or (w + 1) // 2 != w2:
+        raise VfiLibraryError(f"phase_merge: {tuple(gs.shape)} is no phase split of a {h}x{w} tensor")
+    c = c4 // 4
+    if out is None:
+        out = new((n, c, h, w), gs)
+    elif tuple(out.shape) != (n, c, h, w):
+        raise VfiLibraryError(f"phase_merge: out shape {tuple(out.shape)} != {(n, c, h, w)}")
+    gp, gs_ = _slice_ptr(gs, "gs")
+    op, os_ = _slice_ptr(out, "out")
+    _lib.call("vfi_phase_merge", gp, gs_, op, os_, n, c, h, w, _lib.stream_ptr(),
+              work=_prof("byte", 4.0 * n * c * (h * w + 4 * h2 * w2), "phase_merge"))
+    return out
+
+
+# tap k of an axis of the stride-2 filter -> (phase, tap) of the stride-1 filter over the split tensor
+_STRIDE2_TAP = ((1, 0), (0, 1), (1, 1))
+_STRIDE2_INDEX = {}
+
+
+def _stride2_index(device):
+    """For each of the 9 taps (ky, kx) its position among the 36 = (phase 2 py + px, ty, tx) of the expanded filter (cached
+    per device)."""
+    idx = _STRIDE2_INDEX.get(device)
+    if idx is None:
+        pos = [(2 * _STRIDE2_TAP[ky][0] + _STRIDE2_TAP[kx][0]) * 9 + _STRIDE2_TAP[ky][1] * 3 + _STRIDE2_TAP[kx][1]
+               for ky in range(3) for kx in range(3)]
+        idx = _STRIDE2_INDEX[device] = torch.tensor(pos, dtype=torch.long, device=device)
+    return idx
+
+
+def stride2_weight(weight):
+    """(Cout, 4C, 3, 3) filter of the stride-1 convolution over phase_split(x) that equals the 3x3 / stride 2 / pad 1
+    convolution of x with `weight` (Cout, C, 3, 3): 9 of every 36 entries are non-zero."""
+    cout, c, kh, kw = weight.shape
+    if (kh, kw) != (3, 3):
+        raise VfiLibraryError(f"stride2_weight: 3x3 filters only, got {kh}x{kw}")
+    wz = weight.new_zeros((cout, c, 36))
+    wz.index_copy_(2, _stride2_index(weight.device), weight.detach().reshape(cout, c, 9))
+    return wz.view(cout, c, 4, 9).permute(0, 2, 1, 3).reshape(cout, 4 * c, 3, 3)
+
+
+def stride2_weight_gather(dw4):
+    """The adjoint of stride2_weight: (Cout, C, 3, 3) gathered from the (Cout, 4C, 3, 3) gradient of the expanded filter."""
+    cout, c4 = dw4.shape[:2]
+    c = c4 // 4
+    flat = dw4.view(cout, 4, c, 9).permute(0, 2, 1, 3).reshape(cout, c, 36)
+    return flat.index_select(2, _stride2_index(dw4.device)).view(cout, c, 3, 3)
+
+
+def conv2d_stride2(x, pc, act=None, out=None, split=None):
+    """act(conv(x) + bias), 3x3 / stride 2 / zero pad 1, as phase_split + one stride-1 vfi_conv2d; `pc` =
+    PackedConv(stride2_weight(weight), bias).  `split`: phase_split(x) when the caller already has it."""
+    xs = phase_split(x) if split is None else split
+    return conv2d(xs, pc, "zeros", act, out=out)
+
+
+def conv2d_stride2_backward_data(dy, pct, size, out=None):
+    """dX (N, C, H, W), (H, W) = size, of conv2d_stride2 from dy (N, Cout, ceil(H/2), ceil(W/2)); `pct` =
+    packed_transposed(stride2_weight(weight)): vfi_conv2d_backward_data, then phase_merge."""
+    return phase_merge(conv2d_backward_data(dy, pct, "zeros"), size, out=out)
+
+
+def conv2d_stride2_backward_weight(x, dy, bias=True, split=None):
+    """(dW (Cout, C, 3, 3), dbias or None) of conv2d_stride2: vfi_conv2d_backward_weight on phase_split(x) (or `split`),
+    then the gather of the 9 live taps of every 36."""
+    xs = phase_split(x) if split is None else split
+    dw4, db = conv2d_backward_weight(xs, dy, 3, "zeros", bias=bias)
+    return stride2_weight_gather(dw4), db
+
+
+def _matrix(t, rows, cols, name):
+    if t is None:
+        return None
+    if tuple(t.shape) != (rows, cols):
+        raise VfiLibraryError(f"{name} must be {(rows, cols)}, got {tuple(t.shape)}")
+    return _lib.dptr(t.detach(), name)
+
+
+def linear_forward(x, weight, bias=None, slope=1.0):
+    """leaky(x (B, K) weight^T (J, K) + bias) -> (B, J), slope 1 = no activation (vfi_linear_forward)."""
+    b, k = x.shape
+    j = weight.shape[0]
+    y = new((b, j), x)
+    _lib.call("vfi_linear_forward", _matrix(x, b, k, "x"), _matrix(weight, j, k, "weight"),
+              None if bias is None else _vec(bias.detach(), j, "bias"), y.data_ptr(), b, k, j, float(slope), _lib.stream_ptr(),
+              work=_prof("byte", 4.0 * (j * k * ((b + 3) // 4) + b * k + b * j), "linear_forward"))
+    return y
+
+
+def linear_backward(x, weight, y, slope, g, need_x=True, need_w=True, need_bias=True):
+    """(dx (B, K), dw (J, K), dbias (J)) of linear_forward from the gradient g of its output y; an output not needed is None
+    (vfi_linear_backward: one pass over weight for dx and dw together)."""
+    b, j = g.shape
+    k = weight.shape[1] if weight is not None else x.shape[1]
+    dx = new((b, k), g) if need_x else None
+    dw = new((j, k), g) if need_w else None
+    db = new((j,), g) if need_bias else None
+    ptr = lambda t: None if t is None else t.data_ptr()
+    _lib.call("vfi_linear_backward", _matrix(x, b, k, "x") if need_w else None, _matrix(weight, j, k, "weight") if need_x else None,
+              _matrix(y, b, j, "y") if slope != 1.0 else None, float(slope), _matrix(g, b, j, "g"), ptr(dx), ptr(dw), ptr(db),
+              b, k, j, _lib.stream_ptr(),
+              work=_prof("byte", 4.0 * j * k * ((b + 3) // 4) * (int(need_x) + int(need_w)) + 4.0 * b * k * (need_x + need_w),
+                         "linear_backward"))
+    return dx, dw, db
+
+
 def phasenet_emit_low(pred, low_in, max_low):
     """The low level's output (vfi_phasenet_emit_low): pred (N,1,H,W), low_in (N,2,H,W) normalised, max_low (N,) -> (N,1,H,W)."""
     n, c, h, w = pred.shape

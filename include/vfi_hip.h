@@ -584,6 +584,50 @@ int vfi_bn_act_backward(const float *g_t, long long gt_bstride, const float *t, 
                         float *g_y, long long gy_bstride, float *g_gamma, float *g_beta, float *workspace, int N, int C,
                         int HW, vfi_stream_t stream);
 
+/* ------------------------------------------------------------------------------------
+ * The AdaCoF trainer's discriminator (reference src/adacof/losses/discriminator.py)
+ * ---------------------------------------------------------------------------------- */
+
+/* BatchNorm2d (batch statistics) + LeakyReLU(slope) of a discriminator block: vfi_bn_act_forward / vfi_bn_act_backward with
+ * act(z) = z > 0 ? z : slope z, the same kernels and the same fixed-order reductions (statistics: vfi_bn_stats).  The
+ * derivative is read off the sign of the output t, so slope must be positive (VFI_ERR_INVALID_ARG otherwise) and t is
+ * required.  Everything else as the vfi_bn_act_* pair. */
+int vfi_bn_leaky_forward(const float *y, long long y_bstride, const float *mean, const float *var, const float *gamma,
+                         const float *beta, float eps, float slope, float *out, long long out_bstride, int N, int C, int HW,
+                         vfi_stream_t stream);
+int vfi_bn_leaky_backward(const float *g_t, long long gt_bstride, const float *t, long long t_bstride, const float *y,
+                          long long y_bstride, const float *mean, const float *var, const float *gamma, float eps, float slope,
+                          float *g_y, long long gy_bstride, float *g_gamma, float *g_beta, float *workspace, int N, int C,
+                          int HW, vfi_stream_t stream);
+
+/* Phase split: xs (N, 4C, ceil(H/2), ceil(W/2)) from x (N, C, H, W),
+ *   xs[n, (2 py + px) C + c, i, j] = x[n, c, 2 i + py, 2 j + px], zero beyond the edge.
+ * A 3x3 / stride 2 / pad 1 convolution of x is the 3x3 / stride 1 / zero pad 1 vfi_conv2d of xs with the weights expanded to
+ * (Cout, 4C, 3, 3): tap k of an axis goes to (phase, tap) 0 -> (1, 0), 1 -> (0, 1), 2 -> (1, 1); its data gradient is
+ * vfi_conv2d_backward_data followed by vfi_phase_merge, its weight gradient vfi_conv2d_backward_weight on xs.
+ * One read and one write; batch strides in floats; 16-byte accesses when W is a multiple of 8, the strides are multiples
+ * of 4 and the bases are 16-byte aligned, 4-byte ones otherwise. */
+int vfi_phase_split(const float *x, long long x_bstride, float *xs, long long xs_bstride, int N, int C, int H, int W,
+                    vfi_stream_t stream);
+/* The adjoint (and inverse on the image of vfi_phase_split): gx (N, C, H, W) from gs (N, 4C, ceil(H/2), ceil(W/2)); the
+ * positions of the zero fill are dropped. */
+int vfi_phase_merge(const float *gs, long long gs_bstride, float *gx, long long gx_bstride, int N, int C, int H, int W,
+                    vfi_stream_t stream);
+
+/* y (B, J) = leaky(x (B, K) w^T + bias), w (J, K) as nn.Linear holds it, leaky(z) = z > 0 ? z : slope z; slope = 1: no
+ * activation; slope <= 0: VFI_ERR_INVALID_ARG.  bias may be NULL.  Dense row-major operands.  w is streamed once per slice of
+ * four samples (16-byte loads when K is a multiple of 4 and x, w are 16-byte aligned), x comes from the caches; any B >= 1.
+ * Sums in an order fixed by K alone. */
+int vfi_linear_forward(const float *x, const float *w, const float *bias, float *y, int B, int K, int J, float slope,
+                       vfi_stream_t stream);
+/* Adjoint, g (B, J) the gradient of y: gm = g * (y > 0 ? 1 : slope) (y may be NULL when slope = 1),
+ *   dx (B, K) = gm w,  dw (J, K) = gm^T x,  dbias (J) = sum_b gm;  each may be NULL (not produced), not all three.
+ * x may be NULL without dw, w without dx.  One pass: every workgroup owns a slab of columns k and walks j in order, so w is
+ * read once and dw written once when both are wanted (B <= 4; further slices of four samples add to dw in order).  One writer
+ * per element, no atomics. */
+int vfi_linear_backward(const float *x, const float *w, const float *y, float slope, const float *g, float *dx, float *dw,
+                        float *dbias, int B, int K, int J, vfi_stream_t stream);
+
 /* out[0] = scale / count * sum |w(a - b)| over `count` floats, w(d) = atan2(sin d, cos d) when wrap != 0, else d.
  * wrap = 0, scale = 1: nn.L1Loss (loss.py:8,20).  wrap = 1, scale = nbands, a = the target's and b = the output's phases
  * of one level: that level's term of the phase loss, the sum over the orientations of the mean |delta_psi| (loss.py:10-16).

@@ -8,7 +8,10 @@ KernelEstimation as plain torch.nn layers (MIOpen convolutions) on the same GPU 
 `--loss STRING` adds the trainer's step with that `vfi_amd.adacof.losses.Loss` (forward, loss, backward, Adamax step) next
 to the default loss's, and, when the string has a VGG term, the VGG node alone (forward, backward to the image) and torch's
 own nn.Sequential of the same ten layers (MIOpen), forward + backward to the input.  `--vgg-weights FILE` is a torchvision
-vgg16 state dict; without it seeded He-scaled weights are used (the time does not depend on the values)."""
+vgg16 state dict; without it seeded He-scaled weights are used (the time does not depend on the values).  When the string
+has a GAN term (`GAN`, `WGAN`, `FI_GAN`; the discriminator is sized by the frame: patch_size = H) it also prints the
+discriminator alone: forward, and backward to the input and every parameter, next to torch's own
+modules (MIOpen) of the same layers, and the two linear kernels' bytes per second on the 512 (H/16)^2 -> 1024 layer."""
 import argparse
 import os
 import sys
@@ -58,7 +61,8 @@ def loss_section(net, f0, f1, f2, loss_string, vgg_weights, iters, warm):
     opt_args = types.SimpleNamespace(optimizer="ADAMax", lr=1e-3, weight_decay=0)
     net.train(True)
     for string in dict.fromkeys((DEFAULT_LOSS, loss_string)):
-        crit = losses.Loss(types.SimpleNamespace(loss=string, vgg_weights=weights, gpu_id=0))
+        crit = losses.Loss(types.SimpleNamespace(loss=string, vgg_weights=weights, gpu_id=0, patch_size=f0.shape[2],
+                                                 decay_type="step", lr_decay=20, gamma=0.5, **vars(opt_args)))
         opt = utility.make_optimizer(opt_args, net)
 
         def step():
@@ -66,6 +70,8 @@ def loss_section(net, f0, f1, f2, loss_string, vgg_weights, iters, warm):
             crit(net(f0, f2), f1, [f0, f2]).backward()
             opt.step()
         print(f"  trainer step, --loss {string}: {timed(step, iters, warm):8.3f} ms")
+    if "GAN" in loss_string:
+        discriminator_section(f0, iters, warm)
     if "VGG" not in loss_string:
         return
     node = vgg.VGG(weights).to(f0.device)
@@ -94,6 +100,36 @@ def loss_section(net, f0, f1, f2, loss_string, vgg_weights, iters, warm):
         tloss().backward()
     t_ts = timed(tstep, iters, warm)
     print(f"  torch/MIOpen nn.Sequential of the ten layers: forward {t_tf:.3f} ms, backward {t_ts - t_tf:.3f} ms")
+
+
+def discriminator_section(f0, iters, warm):
+    from vfi_amd import ops
+    from vfi_amd.adacof.losses.discriminator import Discriminator
+    torch.manual_seed(0)
+    net = Discriminator(types.SimpleNamespace(patch_size=f0.shape[2]), 'GAN').to(f0.device)
+    x = f0.clone().requires_grad_(True)
+
+    def step(module):
+        x.grad = None
+        module.zero_grad()
+        module(x).sum().backward()
+    t_f = timed(lambda: net(x), iters, warm)
+    t_s = timed(lambda: step(net), iters, warm)
+    print(f"  discriminator alone (HIP node): forward {t_f:.3f} ms, backward {t_s - t_f:.3f} ms")
+    plain = torch.nn.Sequential(net.features, torch.nn.Flatten(), net.classifier)      # the same modules, torch's route
+    t_tf = timed(lambda: plain(x), iters, warm)
+    t_ts = timed(lambda: step(plain), iters, warm)
+    print(f"  torch/MIOpen modules of the same layers: forward {t_tf:.3f} ms, backward {t_ts - t_tf:.3f} ms")
+    lin = net.classifier[0]
+    b, k, j = x.shape[0], lin.in_features, lin.out_features
+    flat = torch.randn((b, k), device=x.device)
+    g = torch.randn((b, j), device=x.device)
+    y = ops.linear_forward(flat, lin.weight, lin.bias, 0.2)
+    t_lf = timed(lambda: ops.linear_forward(flat, lin.weight, lin.bias, 0.2), iters, warm)
+    t_lb = timed(lambda: ops.linear_backward(flat, lin.weight, y, 0.2, g), iters, warm)
+    wb = 4.0 * j * k
+    print(f"  linear {k} -> {j}, B {b}: forward {t_lf:.3f} ms, {wb / t_lf * 1e-9:.2f} TB/s (w read once); backward (dx, dw, dbias) "
+          f"{t_lb:.3f} ms, {2 * wb / t_lb * 1e-9:.2f} TB/s (w read, dw written)")
 
 
 def main(n=4, h=256, w=256, iters=10, warm=3, loss_string=None, vgg_weights=None):
