@@ -2,7 +2,9 @@
 // have:
 //   * the phase split that turns a 3x3 / stride 2 / pad 1 convolution into a 3x3 / stride 1 one over 4C channels, and its
 //     adjoint (the convolutions themselves, forward and both gradients, are vfi_conv2d* on the split tensor);
-//   * the classifier's linear layers with a fused LeakyReLU, forward and backward.
+//   * the classifier's linear layers with a fused LeakyReLU, forward and backward;
+//   * the WGAN_GP term's streaming pieces (section 28): LeakyReLU as a mask read off another tensor's sign, the interpolate
+//     between the fake and the real batch, the gradient penalty and its adjoint.
 // The rules of section 12 hold: no float atomics, one writer per element, every sum in an order fixed by the shape.
 #include "vfi_grad_common.h"
 
@@ -246,7 +248,173 @@ void launch_linear_backward(const float *x, const float *w, const float *y, floa
 #undef VFI_LB
 }
 
+// ---- the WGAN_GP term ----------------------------------------------------------------------------
+// out = s > 0 ? a : slope a.  No __restrict__: s may be a, out may be a (each thread reads its element before it writes it).
+template <typename T>
+__global__ void leaky_mask_kernel(const T *a, long long a_bs, const T *s, long long s_bs, T *out, long long o_bs, int N,
+                                  long long count, float slope) {
+    constexpr int L = sizeof(T) / sizeof(float);
+    GRID_STRIDE(i, (long long)N * count) {
+        const long long n = i / count, e = i - n * count;
+        const T x = a[n * a_bs + e], y = s[n * s_bs + e];
+        T r;
+#pragma unroll
+        for (int l = 0; l < L; ++l) lane_set(r, l, lane_get(y, l) > 0.0f ? lane_get(x, l) : lane_get(x, l) * slope);
+        out[n * o_bs + e] = r;
+    }
+}
+
+// fake (1 - eps) + real eps in four roundings: contraction is off for this function alone, so neither product fuses with
+// the sum (torch's float32 expression rounds each of `1 - eps`, the two `mul`s and the `+`)
+__device__ __forceinline__ float gp_mix_one(float f, float r, float e) {
+#pragma clang fp contract(off)
+    const float om = 1.0f - e;
+    const float p = f * om;
+    const float q = r * e;
+    return p + q;
+}
+template <typename T>
+__global__ void gp_mix_kernel(const T *__restrict__ fake, long long f_bs, const T *__restrict__ real, long long r_bs,
+                              const T *__restrict__ eps, long long e_bs, T *__restrict__ hat, long long h_bs, int N,
+                              long long count) {
+    constexpr int L = sizeof(T) / sizeof(float);
+    GRID_STRIDE(i, (long long)N * count) {
+        const long long n = i / count, e = i - n * count;
+        const T f = fake[n * f_bs + e], r = real[n * r_bs + e], ep = eps[n * e_bs + e];
+        T h;
+#pragma unroll
+        for (int l = 0; l < L; ++l) lane_set(h, l, gp_mix_one(lane_get(f, l), lane_get(r, l), lane_get(ep, l)));
+        hat[n * h_bs + e] = h;
+    }
+}
+
+// norms[b] = sqrt(sum_i g[b][i]^2): workgroup b; thread t takes i = t, t + 256, ... (units of T), alternating between two
+// accumulators per lane (shorter chains, two loads in flight), then (lane sums) and block_sum's tree.
+template <typename T>
+__global__ __launch_bounds__(kThreads) void grad_norm_kernel(const float *__restrict__ g, long long g_bs, float *__restrict__ norms,
+                                                             long long n) {
+    constexpr int L = sizeof(T) / sizeof(float);
+    __shared__ float lds[kThreads];
+    const T *row = reinterpret_cast<const T *>(g + (long long)blockIdx.x * g_bs);
+    const long long nt = n / L;
+    float acc[2][L];
+#pragma unroll
+    for (int l = 0; l < L; ++l) acc[0][l] = acc[1][l] = 0.0f;
+    for (long long k = threadIdx.x; k < nt; k += 2 * kThreads) {
+        const T u = row[k];
+        const bool two = k + kThreads < nt;
+        T w;
+        if (two) w = row[k + kThreads];
+#pragma unroll
+        for (int l = 0; l < L; ++l) {
+            acc[0][l] = fmaf(lane_get(u, l), lane_get(u, l), acc[0][l]);
+            if (two) acc[1][l] = fmaf(lane_get(w, l), lane_get(w, l), acc[1][l]);
+        }
+    }
+    float v[1];
+    if constexpr (L == 4) v[0] = ((acc[0][0] + acc[1][0]) + (acc[0][1] + acc[1][1])) + ((acc[0][2] + acc[1][2]) + (acc[0][3] + acc[1][3]));
+    else v[0] = acc[0][0] + acc[1][0];
+    block_sum<1>(v, lds);
+    if (threadIdx.x == 0) norms[blockIdx.x] = sqrtf(v[0]);
+}
+
+// value = factor * sum_b (norms[b] - 1)^2, one workgroup, the tree fixed by B
+__global__ __launch_bounds__(kThreads) void grad_penalty_value_kernel(const float *__restrict__ norms, int B, float factor,
+                                                                      float *__restrict__ value) {
+    __shared__ float lds[kThreads];
+    float v[1] = {0.0f};
+    for (int b = threadIdx.x; b < B; b += kThreads) {
+        const float d = norms[b] - 1.0f;
+        v[0] += d * d;
+    }
+    block_sum<1>(v, lds);
+    if (threadIdx.x == 0) value[0] = v[0] * factor;
+}
+
+// out[b] = c_b g[b], c_b = upstream 2 weight (norm_b - 1) / (B norm_b) formed in double and rounded once; blockIdx.y = b
+template <typename T>
+__global__ void grad_penalty_backward_kernel(const T *__restrict__ g, long long g_bs, const float *__restrict__ norms,
+                                             const float *__restrict__ up, T *__restrict__ out, long long o_bs, long long nt,
+                                             double two_weight_over_b) {
+    constexpr int L = sizeof(T) / sizeof(float);
+    const int b = blockIdx.y;
+    const double nb = (double)norms[b];
+    const float c = nb == 0.0 ? 0.0f : (float)((double)up[0] * two_weight_over_b * (nb - 1.0) / nb);
+    const T *row = g + (long long)b * g_bs;
+    T *dst = out + (long long)b * o_bs;
+    GRID_STRIDE(i, nt) {
+        const T x = row[i];
+        T r;
+#pragma unroll
+        for (int l = 0; l < L; ++l) lane_set(r, l, nb == 0.0 ? 0.0f : c * lane_get(x, l));
+        dst[i] = r;
+    }
+}
+
 }  // namespace
+
+extern "C" int vfi_leaky_mask(const float *a, long long a_bstride, const float *s, long long s_bstride, float *out,
+                              long long out_bstride, int N, long long count, float slope, vfi_stream_t stream) {
+    VFI_REQUIRE(a && s && out, VFI_ERR_INVALID_ARG, "vfi_leaky_mask: null pointer");
+    VFI_REQUIRE(N > 0 && count > 0, VFI_ERR_INVALID_ARG, "vfi_leaky_mask: bad sizes");
+    VFI_REQUIRE(slope > 0.0f, VFI_ERR_INVALID_ARG, "vfi_leaky_mask: slope %g (must be positive; 1 = no activation)", (double)slope);
+    if (count % 4 == 0 && a_bstride % 4 == 0 && s_bstride % 4 == 0 && out_bstride % 4 == 0 && aligned16(a) && aligned16(s) &&
+        aligned16(out))
+        LAUNCH_1D(leaky_mask_kernel<float4>, (long long)N * count / 4, stream, reinterpret_cast<const float4 *>(a), a_bstride / 4,
+                  reinterpret_cast<const float4 *>(s), s_bstride / 4, reinterpret_cast<float4 *>(out), out_bstride / 4, N,
+                  count / 4, slope);
+    else
+        LAUNCH_1D(leaky_mask_kernel<float>, (long long)N * count, stream, a, a_bstride, s, s_bstride, out, out_bstride, N, count,
+                  slope);
+    return vfi::check_launch("vfi_leaky_mask");
+}
+
+extern "C" int vfi_gp_mix(const float *fake, long long f_bstride, const float *real, long long r_bstride, const float *eps,
+                          long long e_bstride, float *hat, long long h_bstride, int N, long long count, vfi_stream_t stream) {
+    VFI_REQUIRE(fake && real && eps && hat, VFI_ERR_INVALID_ARG, "vfi_gp_mix: null pointer");
+    VFI_REQUIRE(N > 0 && count > 0, VFI_ERR_INVALID_ARG, "vfi_gp_mix: bad sizes");
+    if (count % 4 == 0 && f_bstride % 4 == 0 && r_bstride % 4 == 0 && e_bstride % 4 == 0 && h_bstride % 4 == 0 &&
+        aligned16(fake) && aligned16(real) && aligned16(eps) && aligned16(hat))
+        LAUNCH_1D(gp_mix_kernel<float4>, (long long)N * count / 4, stream, reinterpret_cast<const float4 *>(fake), f_bstride / 4,
+                  reinterpret_cast<const float4 *>(real), r_bstride / 4, reinterpret_cast<const float4 *>(eps), e_bstride / 4,
+                  reinterpret_cast<float4 *>(hat), h_bstride / 4, N, count / 4);
+    else
+        LAUNCH_1D(gp_mix_kernel<float>, (long long)N * count, stream, fake, f_bstride, real, r_bstride, eps, e_bstride, hat,
+                  h_bstride, N, count);
+    return vfi::check_launch("vfi_gp_mix");
+}
+
+extern "C" int vfi_grad_penalty_forward(const float *g, long long g_bstride, float *norms, float *value, int B, long long n,
+                                        float weight, vfi_stream_t stream) {
+    VFI_REQUIRE(g && norms && value, VFI_ERR_INVALID_ARG, "vfi_grad_penalty_forward: null pointer");
+    VFI_REQUIRE(B > 0 && n > 0, VFI_ERR_INVALID_ARG, "vfi_grad_penalty_forward: bad sizes (B = %d, n = %lld)", B, n);
+    hipStream_t s = vfi::as_stream(stream);
+    if (n % 4 == 0 && g_bstride % 4 == 0 && aligned16(g))
+        hipLaunchKernelGGL(grad_norm_kernel<float4>, dim3(B), dim3(kThreads), 0, s, g, g_bstride, norms, n);
+    else
+        hipLaunchKernelGGL(grad_norm_kernel<float>, dim3(B), dim3(kThreads), 0, s, g, g_bstride, norms, n);
+    hipLaunchKernelGGL(grad_penalty_value_kernel, dim3(1), dim3(kThreads), 0, s, norms, B, (float)((double)weight / (double)B), value);
+    return vfi::check_launch("vfi_grad_penalty_forward");
+}
+
+extern "C" int vfi_grad_penalty_backward(const float *g, long long g_bstride, const float *norms, const float *upstream, float *out,
+                                         long long out_bstride, int B, long long n, float weight, vfi_stream_t stream) {
+    VFI_REQUIRE(g && norms && upstream && out, VFI_ERR_INVALID_ARG, "vfi_grad_penalty_backward: null pointer");
+    VFI_REQUIRE(B > 0 && n > 0, VFI_ERR_INVALID_ARG, "vfi_grad_penalty_backward: bad sizes (B = %d, n = %lld)", B, n);
+    VFI_REQUIRE(B <= 65535, VFI_ERR_UNSUPPORTED, "vfi_grad_penalty_backward: B = %d beyond the grid", B);
+    hipStream_t s = vfi::as_stream(stream);
+    const double f = 2.0 * (double)weight / (double)B;
+    if (n % 4 == 0 && g_bstride % 4 == 0 && out_bstride % 4 == 0 && aligned16(g) && aligned16(out)) {
+        const dim3 grid(vfi::blocks_1d(n / 4), B);
+        hipLaunchKernelGGL(grad_penalty_backward_kernel<float4>, grid, dim3(kThreads), 0, s, reinterpret_cast<const float4 *>(g),
+                           g_bstride / 4, norms, upstream, reinterpret_cast<float4 *>(out), out_bstride / 4, n / 4, f);
+    } else {
+        const dim3 grid(vfi::blocks_1d(n), B);
+        hipLaunchKernelGGL(grad_penalty_backward_kernel<float>, grid, dim3(kThreads), 0, s, g, g_bstride, norms, upstream, out,
+                           out_bstride, n, f);
+    }
+    return vfi::check_launch("vfi_grad_penalty_backward");
+}
 
 extern "C" int vfi_phase_split(const float *x, long long x_bstride, float *xs, long long xs_bstride, int N, int C, int H, int W,
                                vfi_stream_t stream) {

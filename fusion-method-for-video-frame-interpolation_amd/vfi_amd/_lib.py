@@ -116,6 +116,10 @@ SIGNATURES = {
     "vfi_phase_merge": [c_f, c_l, c_f, c_l] + [c_i] * 4 + [c_s],
     "vfi_linear_forward": [c_f] * 4 + [c_i] * 3 + [c_fl, c_s],
     "vfi_linear_backward": [c_f] * 3 + [c_fl] + [c_f] * 4 + [c_i] * 3 + [c_s],
+    "vfi_leaky_mask": [c_f, c_l] * 3 + [c_i, c_l, c_fl, c_s],
+    "vfi_gp_mix": [c_f, c_l] * 4 + [c_i, c_l, c_s],
+    "vfi_grad_penalty_forward": [c_f, c_l, c_f, c_f, c_i, c_l, c_fl, c_s],
+    "vfi_grad_penalty_backward": [c_f, c_l, c_f, c_f, c_f, c_l, c_i, c_l, c_fl, c_s],
     "vfi_l1_forward": [c_f, c_f, c_l, c_i, c_fl, c_f, c_f, c_s],
     "vfi_l1_backward": [c_f] * 5 + [c_l, c_i, c_fl, c_s],
     "vfi_triplet_batch_prepare": [c_f, ctypes.c_void_p, c_f, c_l, c_l, c_f, c_l, c_l] + [c_i] * 5 + [c_s],

@@ -21,9 +21,11 @@ Differences from the reference:
   `vfi_amd.evaluation.ssim.SSIMLoss(reduction='mean')`: the mean over the batch of 1 - SSIM, piq's defaults, no weights file.
 * The types `GAN`, `WGAN` and `FI_GAN` build `adversarial.Adversarial(args, type)` (HIP discriminator),
   and `forward` hands `input_frames` to `FI_GAN`, as the reference does.  The classifier of the discriminator is sized by
-  `args.patch_size`: an `args` without one raises NotImplementedError (the discriminator cannot be sized), and so do, always,
-  `WGAN_GP` (its gradient penalty needs a double backward through every kernel) and `T_WGAN_GP` (the temporal discriminator's
-  Conv3d front end is not built).  Any other unknown type raises ValueError; the reference fails there on an unbound name.
+  `args.patch_size`: an `args` without one raises NotImplementedError (the discriminator cannot be sized).  `WGAN_GP` (the
+  critic without BatchNorm plus the gradient penalty) is built when `args.gradient_penalty` is true --
+  the train script's `--gradient_penalty` -- and raises NotImplementedError without it; `T_WGAN_GP` always does (the temporal
+  discriminator's Conv3d front end is not built, and the reference's own penalty branch cannot run it).  Any other unknown
+  type raises ValueError; the reference fails there on an unbound name.
 * The modules move to `cuda:<args.gpu_id>` (the reference: 'cuda', after `set_device(gpu_id)`), and stay where they are when
   there is no device, so the string can be parsed on a host.
 """
@@ -112,10 +114,12 @@ class Loss(nn.modules.loss._Loss):
                 from .vgg import VGG
                 loss_function = VGG(weights=getattr(args, 'vgg_weights', None) or os.environ.get(VGG_WEIGHTS_ENV))
             elif loss_type.find('GAN') >= 0:
-                from .adversarial import TYPES, Adversarial
-                if loss_type not in TYPES:
+                from .adversarial import TYPES, Adversarial, built_types
+                built = built_types(args)       # TYPES, and WGAN_GP when args.gradient_penalty is true
+                if loss_type not in built:
+                    missing = "no temporal discriminator" if len(built) > len(TYPES) else "no gradient penalty, no temporal discriminator"
                     raise NotImplementedError(f"loss type {loss_type!r}: its discriminator is not built (only "
-                                              f"{', '.join(TYPES)}: no gradient penalty, no temporal discriminator)")
+                                              f"{', '.join(built)}: {missing})")
                 if getattr(args, 'patch_size', None) is None:
                     raise NotImplementedError(f"loss type {loss_type!r}: args has no patch_size, which sizes the "
                                               "discriminator's classifier")

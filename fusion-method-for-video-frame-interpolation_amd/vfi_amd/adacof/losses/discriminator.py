@@ -16,10 +16,17 @@ The submodules are real `nn.Conv2d` / `nn.BatchNorm2d` / `nn.Linear`; what runs 
 Either way a forward call in training mode updates `running_mean`, `running_var` (unbiased) and `num_batches_tracked` once, as
 torch's BatchNorm2d does, and a batch with one value per channel raises torch's ValueError.
 
+`Discriminator(args, 'WGAN_GP')` is the reference's variant without BatchNorm (`BasicBlock(..., bn=False)`: state-dict keys
+`features.{i}.0.weight` plus the classifier's four), built only when `args.gradient_penalty` is true.
+On the HIP route it is one autograd node too (`ops.conv2d` -> `ops.leaky_mask` per block, the two `ops.linear_forward`s).
+`input_gradient(x)` returns d sum D(x) / dx as a function of the parameters: on the HIP route a second node whose backward is
+the second-order pass of section 28 -- the existing weight-gradient and forward kernels with the tangent in the input's seat,
+LeakyReLU's second derivative being zero -- and on the plain route torch's `autograd.grad(..., create_graph=True)`.
+
 Differences from the reference:
 
-* `gan_type='WGAN_GP'` and `Temporal_Discriminator` are not built (no double backward through the kernels, no Conv3d):
-  `losses.Loss` refuses those types.
+* `gan_type='WGAN_GP'` needs `args.gradient_penalty` (without it: NotImplementedError, as before it was built), and
+  `Temporal_Discriminator` is not built (no Conv3d): `losses.Loss` refuses `T_WGAN_GP`.
 * `frozen()`: inside it the parameters enter the node detached, so a backward pass forms the input's gradient alone -- the
   generator's pass of `adversarial.Adversarial`, whose weight gradients the reference accumulates and zeroes unused.
 """
@@ -122,9 +129,128 @@ class _DiscriminatorNode(torch.autograd.Function):
         return (None, g_t) + tuple(grads)
 
 
+def _critic_forward(net, x, params):
+    """The no-BatchNorm network, one ops call after the other -> (logits, state).  Per block: convolution (a stride-2 one as
+    a phase split + the stride-1 kernel), then LeakyReLU in place (`leaky_mask` with the output as its own sign).  state:
+    per block (input of the stride-1 convolution, (H, W) of the block's input, effective filter, activation's output)."""
+    saved = []
+    t = x.contiguous()
+    for blk, w in zip(net.features, params[:-4]):
+        size = tuple(t.shape[2:])
+        if blk[0].stride[0] == 2:
+            w_eff, t_in = ops.stride2_weight(w), ops.phase_split(t)
+        else:
+            w_eff, t_in = w.detach(), t
+        y = ops.conv2d(t_in, ops.PackedConv(w_eff), "zeros", None)
+        out = ops.leaky_mask(y, y, SLOPE, out=y)
+        saved.append((t_in, size, w_eff, out))
+        t = out
+    l1w, l1b, l2w, l2b = params[-4:]
+    flat = t.view(t.shape[0], -1)
+    hid = ops.linear_forward(flat, l1w, l1b, SLOPE)
+    logits = ops.linear_forward(hid, l2w, l2b, 1.0)
+    return logits, (saved, flat, hid)
+
+
+def _critic_backward(net, params, state, g, need_x, need_p, keep=None):
+    """First backward of _critic_forward from the gradient g (B, 1) of the logits -> (dx or None, [dparam or None]).
+    `keep`: a list that receives u_1 .. u_10, the gradients at the ten pre-activations, in that order."""
+    saved, flat, hid = state
+    nb = len(saved)
+    grads = [None] * len(params)
+    l1w, l2w = params[nb], params[nb + 2]
+    g = g.contiguous()
+    g_hid, grads[nb + 2], grads[nb + 3] = ops.linear_backward(hid, l2w, None, 1.0, g, True, need_p[nb + 2], need_p[nb + 3])
+    u_hid = ops.leaky_mask(g_hid, hid, SLOPE, out=g_hid)
+    g_flat, grads[nb], grads[nb + 1] = ops.linear_backward(flat, l1w, None, 1.0, u_hid, True, need_p[nb], need_p[nb + 1])
+    us = [u_hid, g]
+    g_t = g_flat.view(saved[-1][3].shape)
+    for i in range(nb - 1, -1, -1):
+        t_in, size, w_eff, out = saved[i]
+        stride2 = net.features[i][0].stride[0] == 2
+        g_y = ops.leaky_mask(g_t, out, SLOPE, out=g_t)
+        us.insert(0, g_y)
+        if need_p[i]:
+            dw, _ = ops.conv2d_backward_weight(t_in, g_y, 3, "zeros", bias=False)
+            grads[i] = ops.stride2_weight_gather(dw) if stride2 else dw
+        if i == 0 and not need_x:
+            g_t = None
+            break
+        g_in = ops.conv2d_backward_data(g_y, ops.packed_transposed(w_eff), "zeros")
+        g_t = ops.phase_merge(g_in, size) if stride2 else g_in
+    if keep is not None:
+        keep.extend(us)
+    return g_t, grads
+
+
+class _CriticNode(torch.autograd.Function):
+    """logits (B, 1) of the WGAN_GP discriminator (no BatchNorm) from x; inputs: net, x, the eight convolution weights, then
+    (linear 1 weight, bias, linear 2 weight, bias)."""
+
+    @staticmethod
+    def forward(ctx, net, x, *params):
+        logits, ctx.state = _critic_forward(net, x, params)
+        ctx.net, ctx.params = net, [p.detach() for p in params]
+        return logits
+
+    @staticmethod
+    def backward(ctx, g):
+        need = ctx.needs_input_grad
+        g_x, grads = _critic_backward(ctx.net, ctx.params, ctx.state, g, need[1], need[2:])
+        return (None, g_x) + tuple(grads)
+
+
+class _InputGradientNode(torch.autograd.Function):
+    """g (B, C, H, W) = d sum_b D(x_b) / d x of the WGAN_GP discriminator, differentiable in the weights (section 28).
+
+    forward: the network's forward and its first backward from u_10 = 1, keeping the activations (their signs s_k) and the
+    gradients u_1 .. u_10 at the pre-activations.  backward, from v_0 = the gradient of g: between the LeakyReLU kinks the
+    network is linear in every weight tensor and LeakyReLU's second derivative is 0, so for k = 1 .. 10
+        dA_k = wgrad(input = v_{k-1}, grad_out = u_k),    v_k = s_k * (A_k v_{k-1})
+    -- the existing weight-gradient kernels with the tangent in the input's seat and the existing forward kernels without
+    bias.  The biases and x get nothing from g."""
+
+    @staticmethod
+    def forward(ctx, net, x, *params):
+        params = [p.detach() for p in params]
+        _, state = _critic_forward(net, x, params)
+        us = []
+        ones = torch.ones((x.shape[0], 1), dtype=torch.float32, device=x.device)
+        g, _ = _critic_backward(net, params, state, ones, True, [False] * len(params), keep=us)
+        ctx.net, ctx.params, ctx.us = net, params, us
+        ctx.signs = [s[3] for s in state[0]] + [state[2]]
+        ctx.filters = [s[2] for s in state[0]]
+        return g
+
+    @staticmethod
+    def backward(ctx, v):
+        need_p = ctx.needs_input_grad[2:]
+        net, params, us, signs = ctx.net, ctx.params, ctx.us, ctx.signs
+        nb = len(ctx.filters)
+        grads = [None] * len(params)
+        v = v.contiguous()
+        for i in range(nb):
+            stride2 = net.features[i][0].stride[0] == 2
+            v_in = ops.phase_split(v) if stride2 else v
+            if need_p[i]:
+                dw, _ = ops.conv2d_backward_weight(v_in, us[i], 3, "zeros", bias=False)
+                grads[i] = ops.stride2_weight_gather(dw) if stride2 else dw
+            w = ops.conv2d(v_in, ops.PackedConv(ctx.filters[i]), "zeros", None)
+            v = ops.leaky_mask(w, signs[i], SLOPE, out=w)
+        flat = v.view(v.shape[0], -1)
+        if need_p[nb]:
+            grads[nb] = ops.linear_backward(flat, None, None, 1.0, us[nb], False, True, False)[1]
+        if need_p[nb + 2]:
+            w = ops.linear_forward(flat, params[nb], None, 1.0)
+            v = ops.leaky_mask(w, signs[nb], SLOPE, out=w)
+            grads[nb + 2] = ops.linear_backward(v, None, None, 1.0, us[nb + 1], False, True, False)[1]
+        return (None, None) + tuple(grads)
+
+
 class _HipRoute:
     """What Discriminator and FI_Discriminator share: the choice of route and the node's argument list."""
     _frozen = False
+    _bn = True
 
     @contextlib.contextmanager
     def frozen(self):
@@ -139,34 +265,34 @@ class _HipRoute:
     def _node_params(self):
         ps = []
         for blk in self.features:
-            ps += [blk[0].weight, blk[1].weight, blk[1].bias]
+            ps += [blk[0].weight, blk[1].weight, blk[1].bias] if self._bn else [blk[0].weight]
         ps += [self.classifier[0].weight, self.classifier[0].bias, self.classifier[2].weight, self.classifier[2].bias]
         return ps
 
-    def _on_hip(self, x):
+    def _on_hip(self, x, needs_x=True):
         ps = self._node_params()
         return (self.training and torch.is_grad_enabled() and x.dim() == 4
                 and all(t.is_cuda and t.dtype == torch.float32 for t in [x] + ps)
-                and (x.requires_grad or any(p.requires_grad for p in ps)))
+                and ((needs_x and x.requires_grad) or any(p.requires_grad for p in ps)))
 
     def _run(self, x):
         if self._on_hip(x):
             ps = self._node_params()
             if self._frozen:
                 ps = [p.detach() for p in ps]
-            return _DiscriminatorNode.apply(self, x, *ps)
+            return (_DiscriminatorNode if self._bn else _CriticNode).apply(self, x, *ps)
         features = self.features(x)
         return self.classifier(features.view(features.size(0), -1))
 
 
-def _build(net, args, in_channels):
-    """Reference discriminator.py:23-51 (and :117-145, which differs in in_channels alone)."""
+def _build(net, args, in_channels, bn=True):
+    """Reference discriminator.py:23-51 (and :117-145, which differs in in_channels alone); bn=False: gan_type 'WGAN_GP'."""
     out_channels = 64
     depth = 7
     act = nn.LeakyReLU(negative_slope=SLOPE, inplace=True)
 
     m_features = [
-        BasicBlock(in_channels, out_channels, 3, bn=True, act=act)
+        BasicBlock(in_channels, out_channels, 3, bn=bn, act=act)
     ]
     for i in range(depth):
         in_channels = out_channels
@@ -176,7 +302,7 @@ def _build(net, args, in_channels):
         else:
             stride = 2
         m_features.append(BasicBlock(
-            in_channels, out_channels, 3, stride=stride, bn=True, act=act
+            in_channels, out_channels, 3, stride=stride, bn=bn, act=act
         ))
 
     net.features = nn.Sequential(*m_features)
@@ -193,13 +319,28 @@ def _build(net, args, in_channels):
 class Discriminator(_HipRoute, nn.Module):
     def __init__(self, args, gan_type='GAN'):
         super(Discriminator, self).__init__()
-        if gan_type == 'WGAN_GP':
+        if gan_type == 'WGAN_GP' and not getattr(args, 'gradient_penalty', False):
             raise NotImplementedError("Discriminator: gan_type 'WGAN_GP' (no BatchNorm, a gradient penalty through a double "
                                       "backward) is not built")
-        _build(self, args, 3)
+        self._bn = gan_type != 'WGAN_GP'
+        _build(self, args, 3, bn=self._bn)
 
     def forward(self, x):
         return self._run(x)
+
+    def input_gradient(self, x):
+        """g (B, C, H, W) = d sum_b D(x_b) / d x, differentiable with respect to the parameters (not to x): what WGAN_GP's
+        gradient penalty is a function of.  The no-BatchNorm variant on the HIP route (training mode, fp32 device tensors,
+        grad enabled, a parameter requiring grad): one autograd node, _InputGradientNode.  Anything else: torch's double
+        backward, `autograd.grad(D(x).sum(), x, create_graph=True)`."""
+        if not self._bn and self._on_hip(x, needs_x=False):
+            ps = self._node_params()
+            if self._frozen:
+                ps = [p.detach() for p in ps]
+            return _InputGradientNode.apply(self, x.detach(), *ps)
+        with torch.enable_grad():
+            x = x.detach().requires_grad_(True)
+            return torch.autograd.grad(self(x).sum(), x, create_graph=True)[0]
 
 
 class FI_Discriminator(_HipRoute, nn.Module):

@@ -3,7 +3,8 @@
 
 The reference's flags and defaults, plus `--vgg_weights` (a torchvision vgg16 state dict for a `VGG` term of `--loss`;
 default: the environment variable VFI_VGG16_WEIGHTS), `--lpips_weights` (the head weights of an `LPIPS` term, which reads
-`--vgg_weights` too; default: VFI_LPIPS_WEIGHTS) and `--workers` (decoding threads of TripletLoader).
+`--vgg_weights` too; default: VFI_LPIPS_WEIGHTS), `--workers` (decoding threads of TripletLoader) and `--gradient_penalty`
+(builds the `WGAN_GP` type of `--loss`, e.g. `--gradient_penalty --loss 1*Charb+0.005*WGAN_GP`; without it that type raises).
 
 Differences from the reference:
 
@@ -50,6 +51,7 @@ parser.add_argument('--vgg_weights', type=str, default=os.environ.get(losses.VGG
 parser.add_argument('--lpips_weights', type=str, default=os.environ.get(losses.LPIPS_WEIGHTS_ENV),
                     help='LPIPS head weights for an LPIPS term (default: $VFI_LPIPS_WEIGHTS)')
 parser.add_argument('--workers', type=int, default=4, help='decoding threads')
+parser.add_argument('--gradient_penalty', action='store_true', help='build the WGAN_GP loss type (critic without BatchNorm + gradient penalty)')
 
 # Optimization specifications
 parser.add_argument('--lr', type=float, default=0.001, help='learning rate')

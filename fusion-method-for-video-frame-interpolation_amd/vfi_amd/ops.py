@@ -1029,6 +1029,61 @@ def linear_backward(x, weight, y, slope, g, need_x=True, need_w=True, need_bias=
     return dx, dw, db
 
 
+# ---- the WGAN_GP term ------------------------------------------------------------------------------
+def _runs(t, name):
+    """(address, batch stride, N, count) of a tensor of N batch-strided dense runs: NCHW (maybe a channel slice) or (B, K)."""
+    if isinstance(t, torch.Tensor) and t.dim() == 2:
+        t = t.unsqueeze(-1).unsqueeze(-1)
+    p, s = _slice_ptr(t, name)
+    return p, s, t.shape[0], t[0].numel()
+
+
+def leaky_mask(a, s, slope, out=None):
+    """s > 0 ? a : slope * a (vfi_leaky_mask) -> out (default: a new tensor).  `s is a`: LeakyReLU itself; `out is a`: the
+    mask of a gradient or of a tangent in place, s the activation's output.  4-d (channel slices allowed) or 2-d tensors."""
+    if tuple(s.shape) != tuple(a.shape) or (out is not None and tuple(out.shape) != tuple(a.shape)):
+        raise VfiLibraryError("leaky_mask: shape mismatch")
+    if out is None:
+        out = torch.empty(tuple(a.shape), dtype=torch.float32, device=a.device)
+    ap, as_, n, count = _runs(a, "a")
+    sp, ss, _, _ = _runs(s, "s")
+    op, os_, _, _ = _runs(out, "out")
+    _lib.call("vfi_leaky_mask", ap, as_, sp, ss, op, os_, n, count, float(slope), _lib.stream_ptr(),
+              work=_prof("byte", 4.0 * n * count * (2 + (sp != ap)), "leaky_mask"))
+    return out
+
+
+def gp_mix(fake, real, eps):
+    """fake * (1 - eps) + real * eps, the bits of that float32 torch expression (vfi_gp_mix): WGAN_GP's interpolate."""
+    if tuple(real.shape) != tuple(fake.shape) or tuple(eps.shape) != tuple(fake.shape):
+        raise VfiLibraryError("gp_mix: shape mismatch")
+    hat = torch.empty(tuple(fake.shape), dtype=torch.float32, device=fake.device)
+    fp, fs, n, count = _runs(fake, "fake")
+    rp, rs, _, _ = _runs(real, "real")
+    ep, es, _, _ = _runs(eps, "eps")
+    _lib.call("vfi_gp_mix", fp, fs, rp, rs, ep, es, hat.data_ptr(), count, n, count, _lib.stream_ptr(),
+              work=_prof("byte", 16.0 * n * count, "gp_mix"))
+    return hat
+
+
+def grad_penalty_forward(g, weight=10.0):
+    """(value 0-d, norms (B,)): norms[b] = ||g[b]||_2, value = weight * mean_b (norms[b] - 1)^2 (vfi_grad_penalty_forward)."""
+    gp, gs, b, n = _runs(g, "g")
+    norms, value = new((b,), g), new((1,), g)
+    _lib.call("vfi_grad_penalty_forward", gp, gs, norms.data_ptr(), value.data_ptr(), b, n, float(weight), _lib.stream_ptr(),
+              work=_prof("byte", 4.0 * b * n, "grad_penalty_forward"))
+    return value[0], norms
+
+
+def grad_penalty_backward(g, norms, upstream, weight=10.0):
+    """upstream * d value / d g, of g's shape; a row of norm 0 gives zeros (vfi_grad_penalty_backward)."""
+    gp, gs, b, n = _runs(g, "g")
+    out = torch.empty(tuple(g.shape), dtype=torch.float32, device=g.device)
+    _lib.call("vfi_grad_penalty_backward", gp, gs, _vec(norms, b, "norms"), _lib.dptr(upstream.reshape(1), "upstream"),
+              out.data_ptr(), n, b, n, float(weight), _lib.stream_ptr(), work=_prof("byte", 8.0 * b * n, "grad_penalty_backward"))
+    return out
+
+
 def phasenet_emit_low(pred, low_in, max_low):
     """The low level's output (vfi_phasenet_emit_low): pred (N,1,H,W), low_in (N,2,H,W) normalised, max_low (N,) -> (N,1,H,W)."""
     n, c, h, w = pred.shape

@@ -628,6 +628,37 @@ int vfi_linear_forward(const float *x, const float *w, const float *bias, float 
 int vfi_linear_backward(const float *x, const float *w, const float *y, float slope, const float *g, float *dx, float *dw,
                         float *dbias, int B, int K, int J, vfi_stream_t stream);
 
+/* ------------------------------------------------------------------------------------
+ * The WGAN_GP term: LeakyReLU as a mask, the interpolate, the gradient penalty (reference
+ * src/adacof/losses/adversarial.py:54-68)
+ * ---------------------------------------------------------------------------------- */
+
+/* out[n][e] = s[n][e] > 0 ? a[n][e] : slope * a[n][e] over N batch-strided runs of `count` floats (strides in floats).
+ * s may be a itself (LeakyReLU of a convolution's output), out may be a itself (the mask of a gradient or of a tangent, in
+ * place, s the activation's output: its sign is the pre-activation's for slope > 0), and all three may be one tensor.
+ * slope <= 0: VFI_ERR_INVALID_ARG, as vfi_bn_leaky_*.  16-byte accesses when count, the strides and the bases allow,
+ * 4-byte ones otherwise: the same bits either way. */
+int vfi_leaky_mask(const float *a, long long a_bstride, const float *s, long long s_bstride, float *out, long long out_bstride,
+                   int N, long long count, float slope, vfi_stream_t stream);
+
+/* hat = fake * (1 - eps) + real * eps per float, eps of fake's shape: the four operations rounded one by one (no fused
+ * multiply-add), so the bits are those of the float32 expression `fake.mul(1 - eps) + real.mul(eps)`.  Layout and access
+ * widths as vfi_leaky_mask; hat aliases no operand. */
+int vfi_gp_mix(const float *fake, long long f_bstride, const float *real, long long r_bstride, const float *eps,
+               long long e_bstride, float *hat, long long h_bstride, int N, long long count, vfi_stream_t stream);
+
+/* norms[b] = ||g[b]||_2 over the n floats of sample b (batch stride g_bstride floats), value[0] = weight / B *
+ * sum_b (norms[b] - 1)^2.  One workgroup per sample: every thread's chain in index order, the lanes of a 16-byte load as
+ * (x + y) + (z + w), then the block tree; a last workgroup of one launch more sums the B terms the same way.  The order is
+ * fixed by n, B and the access width alone. */
+int vfi_grad_penalty_forward(const float *g, long long g_bstride, float *norms, float *value, int B, long long n, float weight,
+                             vfi_stream_t stream);
+
+/* out[b] = upstream[0] * weight * 2 (norms[b] - 1) / (B norms[b]) * g[b]: the gradient of upstream[0] * value to g.  A row
+ * whose norm is 0 gives zeros (torch's norm backward).  The factor of a row is formed once, in double. */
+int vfi_grad_penalty_backward(const float *g, long long g_bstride, const float *norms, const float *upstream, float *out,
+                              long long out_bstride, int B, long long n, float weight, vfi_stream_t stream);
+
 /* out[0] = scale / count * sum |w(a - b)| over `count` floats, w(d) = atan2(sin d, cos d) when wrap != 0, else d.
  * wrap = 0, scale = 1: nn.L1Loss (loss.py:8,20).  wrap = 1, scale = nbands, a = the target's and b = the output's phases
  * of one level: that level's term of the phase loss, the sum over the orientations of the mean |delta_psi| (loss.py:10-16).

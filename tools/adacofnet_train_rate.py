@@ -11,7 +11,10 @@ own nn.Sequential of the same ten layers (MIOpen), forward + backward to the inp
 vgg16 state dict; without it seeded He-scaled weights are used (the time does not depend on the values).  When the string
 has a GAN term (`GAN`, `WGAN`, `FI_GAN`; the discriminator is sized by the frame: patch_size = H) it also prints the
 discriminator alone: forward, and backward to the input and every parameter, next to torch's own
-modules (MIOpen) of the same layers, and the two linear kernels' bytes per second on the 512 (H/16)^2 -> 1024 layer."""
+modules (MIOpen) of the same layers, and the two linear kernels' bytes per second on the 512 (H/16)^2 -> 1024 layer.  When it
+has a `WGAN_GP` term (built with `gradient_penalty=True`) it prints the penalty pass split into the
+forward, the first backward and the second-order pass (with the two penalty kernels), next to the `create_graph` double
+backward of torch's own modules of the same layers."""
 import argparse
 import os
 import sys
@@ -62,6 +65,7 @@ def loss_section(net, f0, f1, f2, loss_string, vgg_weights, iters, warm):
     net.train(True)
     for string in dict.fromkeys((DEFAULT_LOSS, loss_string)):
         crit = losses.Loss(types.SimpleNamespace(loss=string, vgg_weights=weights, gpu_id=0, patch_size=f0.shape[2],
+                                                 gradient_penalty="WGAN_GP" in string.replace("T_WGAN_GP", ""),
                                                  decay_type="step", lr_decay=20, gamma=0.5, **vars(opt_args)))
         opt = utility.make_optimizer(opt_args, net)
 
@@ -72,6 +76,8 @@ def loss_section(net, f0, f1, f2, loss_string, vgg_weights, iters, warm):
         print(f"  trainer step, --loss {string}: {timed(step, iters, warm):8.3f} ms")
     if "GAN" in loss_string:
         discriminator_section(f0, iters, warm)
+    if "WGAN_GP" in loss_string:
+        gradient_penalty_section(f0, f1, iters, warm)
     if "VGG" not in loss_string:
         return
     node = vgg.VGG(weights).to(f0.device)
@@ -130,6 +136,34 @@ def discriminator_section(f0, iters, warm):
     wb = 4.0 * j * k
     print(f"  linear {k} -> {j}, B {b}: forward {t_lf:.3f} ms, {wb / t_lf * 1e-9:.2f} TB/s (w read once); backward (dx, dw, dbias) "
           f"{t_lb:.3f} ms, {2 * wb / t_lb * 1e-9:.2f} TB/s (w read, dw written)")
+
+
+def gradient_penalty_section(f0, f1, iters, warm):
+    """The penalty pass of one WGAN_GP step on hat = mix(f0, f1): forward, first backward, second-order pass."""
+    from vfi_amd import ops
+    from vfi_amd.adacof.losses import adversarial, discriminator
+    torch.manual_seed(0)
+    net = discriminator.Discriminator(types.SimpleNamespace(patch_size=f0.shape[2], gradient_penalty=True), 'WGAN_GP').to(f0.device)
+    hat = ops.gp_mix(f0, f1, torch.rand_like(f0))
+    params = [p.detach() for p in net._node_params()]
+
+    def whole():
+        net.zero_grad(set_to_none=True)
+        adversarial.gradient_penalty(net.input_gradient(hat)).backward()
+    t_f = timed(lambda: discriminator._critic_forward(net, hat, params), iters, warm)
+    t_g = timed(lambda: net.input_gradient(hat), iters, warm)
+    t_w = timed(whole, iters, warm)
+    print(f"  gradient penalty pass (HIP nodes): forward {t_f:.3f} ms, first backward {t_g - t_f:.3f} ms, second-order pass + "
+          f"penalty kernels {t_w - t_g:.3f} ms, together {t_w:.3f} ms")
+    net.eval()                                   # the plain-torch route of the same modules (no BatchNorm: the same function)
+
+    def plain_whole():
+        net.zero_grad(set_to_none=True)
+        g = net.input_gradient(hat)
+        (10 * g.view(g.size(0), -1).norm(2, dim=1).sub(1).pow(2).mean()).backward()
+    t_p = timed(plain_whole, iters, warm)
+    print(f"  torch/MIOpen create_graph double backward of the same layers, penalty and its backward: {t_p:.3f} ms")
+    net.train()
 
 
 def main(n=4, h=256, w=256, iters=10, warm=3, loss_string=None, vgg_weights=None):
