@@ -19,6 +19,8 @@ torch's BatchNorm2d does, and a batch with one value per channel raises torch's 
 `Discriminator(args, 'WGAN_GP')` is the reference's variant without BatchNorm (`BasicBlock(..., bn=False)`: state-dict keys
 `features.{i}.0.weight` plus the classifier's four), built only when `args.gradient_penalty` is true.
 On the HIP route it is one autograd node too (`ops.conv2d` -> `ops.leaky_mask` per block, the two `ops.linear_forward`s).
+Both nodes are `_walk_forward` / `_walk_backward` over the eight blocks and the classifier, BatchNorm being a stage that the
+network has or has not; a block's convolution and its adjoint, stride 1 or 2, are `_block_forward` / `_block_backward`.
 `input_gradient(x)` returns d sum D(x) / dx as a function of the parameters: on the HIP route a second node whose backward is
 the second-order pass of section 28 -- the existing weight-gradient and forward kernels with the tangent in the input's seat,
 LeakyReLU's second derivative being zero -- and on the plain route torch's `autograd.grad(..., create_graph=True)`.
@@ -65,86 +67,56 @@ def _update_running(bn, mean, var, count):
         bn.running_var.mul_(1.0 - m).add_(var, alpha=m * count / (count - 1.0))
 
 
-class _DiscriminatorNode(torch.autograd.Function):
-    """logits (B, 1) of the whole network from x (B, C, H, W); inputs: net, x, then per block (conv.weight, bn.weight, bn.bias),
-    then (linear 1 weight, bias, linear 2 weight, bias)."""
-
-    @staticmethod
-    def forward(ctx, net, x, *params):
-        blocks = list(net.features)
-        saved = []
-        t = x.contiguous()
-        for i, blk in enumerate(blocks):
-            conv, bn = blk[0], blk[1]
-            w, gamma, beta = params[3 * i:3 * i + 3]
-            n, _, h, wd = t.shape
-            if conv.stride[0] == 2:
-                w_eff = ops.stride2_weight(w)
-                t_in = ops.phase_split(t)
-            else:
-                w_eff, t_in = w.detach(), t
-            y = ops.conv2d(t_in, ops.PackedConv(w_eff), "zeros", None)
-            mean, var = ops.bn_stats(y)
-            _update_running(bn, mean, var, y.shape[0] * y.shape[2] * y.shape[3])
-            out = ops.bn_leaky_forward(y, mean, var, gamma, beta, bn.eps, SLOPE)
-            saved.append((t_in, (h, wd), w_eff, y, mean, var, out))
-            t = out
-        l1w, l1b, l2w, l2b = params[3 * len(blocks):]
-        flat = t.view(t.shape[0], -1)
-        hid = ops.linear_forward(flat, l1w, l1b, SLOPE)
-        logits = ops.linear_forward(hid, l2w, l2b, 1.0)
-        ctx.blocks, ctx.saved, ctx.flat, ctx.hid = blocks, saved, flat, hid
-        ctx.params = [p.detach() for p in params]
-        return logits
-
-    @staticmethod
-    def backward(ctx, g):
-        need = ctx.needs_input_grad
-        need_x, need_p = need[1], need[2:]
-        blocks, params, nb = ctx.blocks, ctx.params, len(ctx.blocks)
-        grads = [None] * len(params)
-        l1w, l1b, l2w, l2b = params[3 * nb:]
-        q = 3 * nb
-        g_hid, grads[q + 2], grads[q + 3] = ops.linear_backward(ctx.hid, l2w, None, 1.0, g.contiguous(), True, need_p[q + 2],
-                                                                need_p[q + 3])
-        g_flat, grads[q], grads[q + 1] = ops.linear_backward(ctx.flat, l1w, ctx.hid, SLOPE, g_hid, True, need_p[q], need_p[q + 1])
-        g_t = g_flat.view(ctx.saved[-1][6].shape)
-        for i in range(nb - 1, -1, -1):
-            t_in, size, w_eff, y, mean, var, out = ctx.saved[i]
-            bn = blocks[i][1]
-            stride2 = blocks[i][0].stride[0] == 2
-            g_y, g_gamma, g_beta = ops.bn_leaky_backward(g_t, out, y, mean, var, params[3 * i + 1], bn.eps, SLOPE, out=g_t)
-            if need_p[3 * i + 1]:
-                grads[3 * i + 1] = g_gamma
-            if need_p[3 * i + 2]:
-                grads[3 * i + 2] = g_beta
-            if need_p[3 * i]:
-                dw, _ = ops.conv2d_backward_weight(t_in, g_y, 3, "zeros", bias=False)
-                grads[3 * i] = ops.stride2_weight_gather(dw) if stride2 else dw
-            if i == 0 and not need_x:
-                g_t = None
-                break
-            g_in = ops.conv2d_backward_data(g_y, ops.packed_transposed(w_eff), "zeros")
-            g_t = ops.phase_merge(g_in, size) if stride2 else g_in
-        return (None, g_t) + tuple(grads)
+def _split(conv, t):
+    """What the stride-1 kernels of a block read: its input t, or t's phase split when the block has stride 2."""
+    return ops.phase_split(t) if conv.stride[0] == 2 else t
 
 
-def _critic_forward(net, x, params):
-    """The no-BatchNorm network, one ops call after the other -> (logits, state).  Per block: convolution (a stride-2 one as
-    a phase split + the stride-1 kernel), then LeakyReLU in place (`leaky_mask` with the output as its own sign).  state:
-    per block (input of the stride-1 convolution, (H, W) of the block's input, effective filter, activation's output)."""
+def _block_forward(conv, t, w=None, w_eff=None, split=None):
+    """A block's convolution of t -> (split input, (H, W) of t, effective filter, pre-activation).  The filter is made from
+    the weight w, or is `w_eff` of an earlier call; `split`: _split(conv, t) when the caller already has it."""
+    stride2 = conv.stride[0] == 2
+    if w_eff is None:
+        w_eff = ops.stride2_weight(w) if stride2 else w.detach()
+    if split is None:
+        split = _split(conv, t)
+    pc = ops.PackedConv(w_eff)
+    y = ops.conv2d_stride2(t, pc, split=split) if stride2 else ops.conv2d(t, pc, "zeros", None)
+    return split, tuple(t.shape[2:]), w_eff, y
+
+
+def _block_backward(conv, t_in, size, w_eff, g_y, need_w, need_x=False):
+    """The adjoint of _block_forward from g_y, the gradient at the pre-activation -> (weight gradient, gradient of the
+    block's input), each None when not needed."""
+    stride2 = conv.stride[0] == 2
+    dw = g_in = None
+    if need_w:
+        dw = (ops.conv2d_stride2_backward_weight(None, g_y, bias=False, split=t_in) if stride2
+              else ops.conv2d_backward_weight(t_in, g_y, 3, "zeros", bias=False))[0]
+    if need_x:
+        pct = ops.packed_transposed(w_eff)
+        g_in = ops.conv2d_stride2_backward_data(g_y, pct, size) if stride2 else ops.conv2d_backward_data(g_y, pct, "zeros")
+    return dw, g_in
+
+
+def _walk_forward(net, x, params):
+    """The network, one ops call after the other -> (logits, state).  Per block: the convolution, then with BatchNorm the
+    batch statistics, the running ones' update and `bn_leaky_forward`; without, LeakyReLU in place (`leaky_mask` with the
+    output as its own sign).  params: as _node_params() orders them.  state: (per block (input of the stride-1 convolution,
+    (H, W) of the block's input, effective filter, activation's output[, pre-activation, mean, var]), flat, hid)."""
+    k = 3 if net._bn else 1
     saved = []
     t = x.contiguous()
-    for blk, w in zip(net.features, params[:-4]):
-        size = tuple(t.shape[2:])
-        if blk[0].stride[0] == 2:
-            w_eff, t_in = ops.stride2_weight(w), ops.phase_split(t)
+    for i, blk in enumerate(net.features):
+        t_in, size, w_eff, y = _block_forward(blk[0], t, params[k * i])
+        if net._bn:
+            mean, var = ops.bn_stats(y)
+            _update_running(blk[1], mean, var, y.shape[0] * y.shape[2] * y.shape[3])
+            t = ops.bn_leaky_forward(y, mean, var, params[k * i + 1], params[k * i + 2], blk[1].eps, SLOPE)
+            saved.append((t_in, size, w_eff, t, y, mean, var))
         else:
-            w_eff, t_in = w.detach(), t
-        y = ops.conv2d(t_in, ops.PackedConv(w_eff), "zeros", None)
-        out = ops.leaky_mask(y, y, SLOPE, out=y)
-        saved.append((t_in, size, w_eff, out))
-        t = out
+            t = ops.leaky_mask(y, y, SLOPE, out=y)
+            saved.append((t_in, size, w_eff, t))
     l1w, l1b, l2w, l2b = params[-4:]
     flat = t.view(t.shape[0], -1)
     hid = ops.linear_forward(flat, l1w, l1b, SLOPE)
@@ -152,52 +124,67 @@ def _critic_forward(net, x, params):
     return logits, (saved, flat, hid)
 
 
-def _critic_backward(net, params, state, g, need_x, need_p, keep=None):
-    """First backward of _critic_forward from the gradient g (B, 1) of the logits -> (dx or None, [dparam or None]).
+def _walk_backward(net, params, state, g, need_x, need_p, keep=None):
+    """First backward of _walk_forward from the gradient g (B, 1) of the logits -> (dx or None, [dparam or None]).
     `keep`: a list that receives u_1 .. u_10, the gradients at the ten pre-activations, in that order."""
     saved, flat, hid = state
-    nb = len(saved)
+    k = 3 if net._bn else 1
+    q = k * len(saved)
     grads = [None] * len(params)
-    l1w, l2w = params[nb], params[nb + 2]
+    l1w, l2w = params[q], params[q + 2]
     g = g.contiguous()
-    g_hid, grads[nb + 2], grads[nb + 3] = ops.linear_backward(hid, l2w, None, 1.0, g, True, need_p[nb + 2], need_p[nb + 3])
-    u_hid = ops.leaky_mask(g_hid, hid, SLOPE, out=g_hid)
-    g_flat, grads[nb], grads[nb + 1] = ops.linear_backward(flat, l1w, None, 1.0, u_hid, True, need_p[nb], need_p[nb + 1])
-    us = [u_hid, g]
+    g_hid, grads[q + 2], grads[q + 3] = ops.linear_backward(hid, l2w, None, 1.0, g, True, need_p[q + 2], need_p[q + 3])
+    if net._bn:
+        g_flat, grads[q], grads[q + 1] = ops.linear_backward(flat, l1w, hid, SLOPE, g_hid, True, need_p[q], need_p[q + 1])
+    else:                                                               # masked apart: u_9 is kept for the second-order pass
+        g_hid = ops.leaky_mask(g_hid, hid, SLOPE, out=g_hid)
+        g_flat, grads[q], grads[q + 1] = ops.linear_backward(flat, l1w, None, 1.0, g_hid, True, need_p[q], need_p[q + 1])
+    us = [g_hid, g]
     g_t = g_flat.view(saved[-1][3].shape)
-    for i in range(nb - 1, -1, -1):
-        t_in, size, w_eff, out = saved[i]
-        stride2 = net.features[i][0].stride[0] == 2
-        g_y = ops.leaky_mask(g_t, out, SLOPE, out=g_t)
+    for i in range(len(saved) - 1, -1, -1):
+        t_in, size, w_eff, out = saved[i][:4]
+        if net._bn:
+            y, mean, var = saved[i][4:]
+            g_y, g_gamma, g_beta = ops.bn_leaky_backward(g_t, out, y, mean, var, params[k * i + 1], net.features[i][1].eps, SLOPE,
+                                                         out=g_t)
+            if need_p[k * i + 1]:
+                grads[k * i + 1] = g_gamma
+            if need_p[k * i + 2]:
+                grads[k * i + 2] = g_beta
+        else:
+            g_y = ops.leaky_mask(g_t, out, SLOPE, out=g_t)
         us.insert(0, g_y)
-        if need_p[i]:
-            dw, _ = ops.conv2d_backward_weight(t_in, g_y, 3, "zeros", bias=False)
-            grads[i] = ops.stride2_weight_gather(dw) if stride2 else dw
-        if i == 0 and not need_x:
-            g_t = None
-            break
-        g_in = ops.conv2d_backward_data(g_y, ops.packed_transposed(w_eff), "zeros")
-        g_t = ops.phase_merge(g_in, size) if stride2 else g_in
+        grads[k * i], g_t = _block_backward(net.features[i][0], t_in, size, w_eff, g_y, need_p[k * i], i > 0 or need_x)
     if keep is not None:
         keep.extend(us)
     return g_t, grads
 
 
-class _CriticNode(torch.autograd.Function):
-    """logits (B, 1) of the WGAN_GP discriminator (no BatchNorm) from x; inputs: net, x, the eight convolution weights, then
-    (linear 1 weight, bias, linear 2 weight, bias)."""
+class _WalkNode(torch.autograd.Function):
+    """logits (B, 1) of the whole network from x (B, C, H, W); inputs: net, x, then the parameters as _node_params() orders
+    them."""
 
     @staticmethod
     def forward(ctx, net, x, *params):
-        logits, ctx.state = _critic_forward(net, x, params)
+        logits, ctx.state = _walk_forward(net, x, params)
         ctx.net, ctx.params = net, [p.detach() for p in params]
         return logits
 
     @staticmethod
     def backward(ctx, g):
         need = ctx.needs_input_grad
-        g_x, grads = _critic_backward(ctx.net, ctx.params, ctx.state, g, need[1], need[2:])
+        g_x, grads = _walk_backward(ctx.net, ctx.params, ctx.state, g, need[1], need[2:])
         return (None, g_x) + tuple(grads)
+
+
+class _DiscriminatorNode(_WalkNode):
+    """The walk with BatchNorm: per block (conv.weight, bn.weight, bn.bias), then (linear 1 weight, bias, linear 2 weight,
+    bias)."""
+
+
+class _CriticNode(_WalkNode):
+    """The walk of the WGAN_GP discriminator (no BatchNorm): the eight convolution weights, then (linear 1 weight, bias,
+    linear 2 weight, bias)."""
 
 
 class _InputGradientNode(torch.autograd.Function):
@@ -213,10 +200,10 @@ class _InputGradientNode(torch.autograd.Function):
     @staticmethod
     def forward(ctx, net, x, *params):
         params = [p.detach() for p in params]
-        _, state = _critic_forward(net, x, params)
+        _, state = _walk_forward(net, x, params)
         us = []
         ones = torch.ones((x.shape[0], 1), dtype=torch.float32, device=x.device)
-        g, _ = _critic_backward(net, params, state, ones, True, [False] * len(params), keep=us)
+        g, _ = _walk_backward(net, params, state, ones, True, [False] * len(params), keep=us)
         ctx.net, ctx.params, ctx.us = net, params, us
         ctx.signs = [s[3] for s in state[0]] + [state[2]]
         ctx.filters = [s[2] for s in state[0]]
@@ -230,12 +217,10 @@ class _InputGradientNode(torch.autograd.Function):
         grads = [None] * len(params)
         v = v.contiguous()
         for i in range(nb):
-            stride2 = net.features[i][0].stride[0] == 2
-            v_in = ops.phase_split(v) if stride2 else v
-            if need_p[i]:
-                dw, _ = ops.conv2d_backward_weight(v_in, us[i], 3, "zeros", bias=False)
-                grads[i] = ops.stride2_weight_gather(dw) if stride2 else dw
-            w = ops.conv2d(v_in, ops.PackedConv(ctx.filters[i]), "zeros", None)
+            conv = net.features[i][0]
+            v_in = _split(conv, v)
+            grads[i] = _block_backward(conv, v_in, None, None, us[i], need_p[i])[0]
+            w = _block_forward(conv, v, w_eff=ctx.filters[i], split=v_in)[3]
             v = ops.leaky_mask(w, signs[i], SLOPE, out=w)
         flat = v.view(v.shape[0], -1)
         if need_p[nb]:

@@ -47,11 +47,11 @@ DEFAULT_LOSS = "1*Charb+0.01*g_Spatial+0.005*g_Occlusion"
 
 def seeded_vgg16_state(seed=0):
     """He-scaled weights under torchvision's keys features.{0,...,21}.{weight,bias}"""
-    from vfi_amd.adacof.losses import vgg
+    from vfi_amd import vgg16
     g = torch.Generator().manual_seed(seed)
     sd = {}
-    for i, idx in enumerate(vgg.CONV_INDICES):
-        cin, cout = vgg.CHANNELS[i], vgg.CHANNELS[i + 1]
+    for i, idx in enumerate(vgg16.CONV_INDICES[:10]):
+        cin, cout = vgg16.CHANNELS[i], vgg16.CHANNELS[i + 1]
         sd[f"features.{idx}.weight"] = torch.randn((cout, cin, 3, 3), generator=g) * (2.0 / (9 * cin)) ** 0.5
         sd[f"features.{idx}.bias"] = torch.randn((cout,), generator=g) * 0.05
     return sd
@@ -150,7 +150,7 @@ def gradient_penalty_section(f0, f1, iters, warm):
     def whole():
         net.zero_grad(set_to_none=True)
         adversarial.gradient_penalty(net.input_gradient(hat)).backward()
-    t_f = timed(lambda: discriminator._critic_forward(net, hat, params), iters, warm)
+    t_f = timed(lambda: discriminator._walk_forward(net, hat, params), iters, warm)
     t_g = timed(lambda: net.input_gradient(hat), iters, warm)
     t_w = timed(whole, iters, warm)
     print(f"  gradient penalty pass (HIP nodes): forward {t_f:.3f} ms, first backward {t_g - t_f:.3f} ms, second-order pass + "
