@@ -129,7 +129,24 @@ SIGNATURES = {
     "vfi_ssim_loss_forward": [c_f, c_l, c_f, c_l, c_f, c_f] + [c_i] * 5 + [c_fl] * 3 + [c_s],
     "vfi_ssim_loss_backward": [c_f, c_l, c_f, c_l, c_f, c_f, c_l] + [c_i] * 5 + [c_fl] * 3 + [c_s],
     "vfi_avg_pool_backward": [c_f, c_f, c_i, c_i, c_i, c_i, c_s],
+    "vfi_optim_step": [c_i, ctypes.c_void_p, c_i, ctypes.c_void_p, c_s],
+    "vfi_optim_limits": [ctypes.POINTER(c_l), ctypes.POINTER(c_i), ctypes.POINTER(c_i), ctypes.POINTER(c_l)],
 }
+
+
+class OptimTensor(ctypes.Structure):
+    """vfi_optim_tensor"""
+    _fields_ = [("param", c_f), ("grad", c_f), ("state0", c_f), ("state1", c_f), ("numel", c_l)]
+
+
+class OptimHyper(ctypes.Structure):
+    """vfi_optim_hyper"""
+    _fields_ = [(n, c_d) for n in ("lr", "beta1", "beta2", "alpha", "eps", "weight_decay", "momentum", "dampening",
+                                   "bias_correction1", "bias_correction2", "clamp_min", "clamp_max")] + \
+               [(n, c_i) for n in ("nesterov", "first_step", "has_clamp")]
+
+
+OPTIM_KINDS = {"sgd": 0, "adam": 1, "adamax": 2, "rmsprop": 3}     # VFI_OPTIM_*
 REDUCE_WORKSPACE_FLOATS = 4096      # VFI_REDUCE_WORKSPACE_FLOATS
 PHASENET_HEAD_WORKSPACE_FLOATS = 1024 * 520     # VFI_PHASENET_HEAD_WORKSPACE_FLOATS
 PHASENET_HEAD_N_WORKSPACE_FLOATS = 1024 * 780   # VFI_PHASENET_HEAD_N_WORKSPACE_FLOATS (twelve predictions: three input images)

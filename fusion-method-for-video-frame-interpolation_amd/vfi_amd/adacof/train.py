@@ -60,6 +60,7 @@ parser.add_argument('--decay_type', type=str, default='step', help='learning rat
 parser.add_argument('--gamma', type=float, default=0.5, help='learning rate decay factor for step decay')
 parser.add_argument('--optimizer', default='ADAMax', choices=('SGD', 'ADAM', 'RMSprop', 'ADAMax'), help='optimizer to use (SGD | ADAM | RMSprop | ADAMax)')
 parser.add_argument('--weight_decay', type=float, default=0, help='weight decay')
+parser.add_argument('--device_optimizer', action='store_true', help='optimiser steps (the discriminators\' too) in one HIP pass (vfi_amd.optim)')
 
 # Options for AdaCoF
 parser.add_argument('--kernel_size', type=int, default=5)

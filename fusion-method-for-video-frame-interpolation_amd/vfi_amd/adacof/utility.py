@@ -78,8 +78,12 @@ _OPTIMIZERS = {"SGD": (optim.SGD, {"momentum": 0.9}),
 
 def make_optimizer(args, my_model):
     """args.optimizer in SGD | ADAM | ADAMax | RMSprop with args.lr and args.weight_decay over the parameters that
-    require grad (utility.py:19-44)."""
+    require grad (utility.py:19-44).  With a true args.device_optimizer (absent = false) it is vfi_amd.optim's subclass of
+    that torch class."""
     cls, kwargs = _OPTIMIZERS[args.optimizer]
+    if getattr(args, 'device_optimizer', False):      # the same class with its step on the device (vfi_amd/optim.py)
+        from .. import optim as device_optim
+        cls = getattr(device_optim, cls.__name__)
     trainable = [p for p in my_model.parameters() if p.requires_grad]
     return cls(trainable, lr=args.lr, weight_decay=args.weight_decay, **kwargs)
 

@@ -47,6 +47,7 @@ parser.add_argument('--workers', type=int, default=4, help='decoding threads')
 parser.add_argument('--lr', type=float, default=1e-4, help='learning rate')
 parser.add_argument('--lr_decay', type=int, default=0, help='learning rate decay per N epochs')
 parser.add_argument('--weight_decay', type=float, default=0, help='weight decay')
+parser.add_argument('--device_optimizer', action='store_true', help='optimiser step in one HIP pass (vfi_amd.optim.Adam)')
 
 # Save Residuals
 parser.add_argument('--save', type=bool, default=False, help='Save Residuals or not')

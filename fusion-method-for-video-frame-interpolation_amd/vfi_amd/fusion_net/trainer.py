@@ -64,7 +64,10 @@ class Trainer:
         self.fusion_net.train()
 
         self.out_dir = out_dir
-        self.optimizer = torch.optim.Adam(self.fusion_net.parameters(), lr=lr, weight_decay=weight_decay)
+        adam = torch.optim.Adam
+        if getattr(args, "device_optimizer", False):      # the same class with its step on the device (vfi_amd/optim.py)
+            from ..optim import Adam as adam
+        self.optimizer = adam(self.fusion_net.parameters(), lr=lr, weight_decay=weight_decay)
         self.result_dir = self.out_dir + "/result"
         self.ckpt_dir = self.out_dir + "/checkpoint"
         self.create_folders()

@@ -4,6 +4,7 @@ Tensors are torch HIP tensors used purely as device-memory handles; every wrappe
 library call on torch's current stream.  Inputs / outputs may be CHANNEL SLICES of wider NCHW
 tensors (`t[:, a:b]`): only the batch stride is free, the (C, H, W) block must be dense.
 """
+import ctypes
 import os
 
 import torch
@@ -1402,3 +1403,48 @@ def triplet_batch_prepare(src, params, size, rgb=True, lab=True):
     _lib.call("vfi_triplet_batch_prepare", _lib.dptr(src, "src", torch.uint8), params.data_ptr(), rp, rs, rb, lp, ls, lb,
               b, hs, ws, h, w, _lib.stream_ptr(), work=("byte", float(moved), "triplet_batch_prepare"))
     return rgb, lab
+
+
+def optim_limits():
+    """(elements per chunk, tensors per launch, chunks per launch, largest numel) of vfi_optim_step; needs no device."""
+    c, m = ctypes.c_longlong(), ctypes.c_longlong()
+    t, k = ctypes.c_int(), ctypes.c_int()
+    _lib.check(_lib.lib().vfi_optim_limits(ctypes.byref(c), ctypes.byref(t), ctypes.byref(k), ctypes.byref(m)),
+               "vfi_optim_limits")
+    return c.value, t.value, k.value, m.value
+
+
+def optim_step(kind, params, grads, state0=None, state1=None, *, lr, betas=(0.0, 0.0), alpha=0.0, eps=0.0, weight_decay=0.0,
+               momentum=0.0, dampening=0.0, nesterov=False, first_step=False, step=1, clamp=None):
+    """One optimiser update of the tensors `params`, which share these hyper-parameters and the step count `step` (the count
+    AFTER this update, 1 for the first): kind in sgd | adam | adamax | rmsprop; include/vfi_hip.h gives the formulas and
+    which state goes where.  params, grads, state0, state1: equally long lists of contiguous float32 tensors on the current
+    HIP device (a state list may be None where the kind keeps no such state).  Everything is written in place through raw
+    pointers, so no version counter moves: vfi_amd.optim bumps them."""
+    n = len(params)
+    if n == 0:
+        return
+    dev, f32 = torch.cuda.current_device(), torch.float32
+    lists = [("param", params), ("grad", grads)] + [(nm, s) for nm, s in (("state0", state0), ("state1", state1)) if s is not None]
+    recs = (_lib.OptimTensor * n)()
+    total = 0
+    for name, tensors in lists:
+        if len(tensors) != n:
+            raise VfiLibraryError(f"optim_step: {len(tensors)} {name} tensors for {n} params")
+        for i, t in enumerate(tensors):
+            if not (t.is_cuda and t.device.index == dev and t.dtype is f32 and t.is_contiguous()
+                    and t.numel() == params[i].numel()):
+                raise VfiLibraryError(f"optim_step: {name} {i} must be a contiguous float32 tensor of its param's size on "
+                                      f"cuda:{dev} (vfi_amd has no CPU path)")
+            setattr(recs[i], name, t.data_ptr())
+    for i, p in enumerate(params):
+        recs[i].numel = p.numel()
+        total += recs[i].numel
+    step = float(step)
+    h = _lib.OptimHyper(lr=lr, beta1=betas[0], beta2=betas[1], alpha=alpha, eps=eps, weight_decay=weight_decay,
+                        momentum=momentum, dampening=dampening, bias_correction1=1 - betas[0] ** step,
+                        bias_correction2=1 - betas[1] ** step, nesterov=int(nesterov), first_step=int(first_step))
+    if clamp is not None:
+        h.clamp_min, h.clamp_max, h.has_clamp = float(clamp[0]), float(clamp[1]), 1
+    _lib.call("vfi_optim_step", _lib.OPTIM_KINDS[kind], ctypes.addressof(recs), n, ctypes.addressof(h), _lib.stream_ptr(),
+              work=("byte", 4.0 * (2 * len(lists) - 1) * total, "optim_" + kind))

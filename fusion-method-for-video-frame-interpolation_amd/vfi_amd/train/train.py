@@ -44,6 +44,7 @@ parser.add_argument('--fixed_stats', action='store_true', help='BatchNorm on the
 parser.add_argument('--lr', type=float, default=1e-3, help='learning rate')
 parser.add_argument('--lr_decay', type=int, default=0, help='learning rate decay per N epochs')
 parser.add_argument('--weight_decay', type=float, default=0, help='weight decay')
+parser.add_argument('--device_optimizer', action='store_true', help='optimiser step in one HIP pass (vfi_amd.optim.Adam)')
 
 # Method Settings
 parser.add_argument('--mode', type=str, default='phase', help='phase, fusion')

@@ -100,7 +100,10 @@ class Trainer:
             raise ValueError(f"Trainer: mode {args.mode!r} is neither 'phase' nor 'fusion'")
         self.model.fine_tune(True, batch_stats=not getattr(args, "fixed_stats", False), fusion=self.fusion)
 
-        self.optimizer = torch.optim.Adam(self.model.parameters(), lr=lr, weight_decay=weight_decay)
+        adam = torch.optim.Adam
+        if getattr(args, "device_optimizer", False):      # the same class with its step on the device (vfi_amd/optim.py)
+            from ..optim import Adam as adam
+        self.optimizer = adam(self.model.parameters(), lr=lr, weight_decay=weight_decay)
         self.result_dir = self.out_dir + "/result"
         self.ckpt_dir = self.out_dir + "/checkpoint"
         self.create_folders()

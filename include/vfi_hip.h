@@ -950,6 +950,55 @@ int vfi_ssim_loss_backward(const float *x, long long x_bstride, const float *y, 
  * the rows and columns the floor drops get exactly 0. */
 int vfi_avg_pool_backward(const float *grad, float *grad_x, int planes, int H, int W, int f, vfi_stream_t stream);
 
+/* ------------------------------------------------------------------------------------
+ * Optimiser step (torch.optim.SGD / Adam / Adamax / RMSprop as the trainers configure them): one multi-tensor pass that
+ * reads and writes every element once.  DESIGN.md section 29.  The arithmetic restates torch/optim's _single_tensor_*
+ * functions operation by operation in fp32 (no contraction); every scalar is derived in double and rounded once.
+ *   SGD      g += wd p;  buf = g on first_step, else momentum buf + (1 - dampening) g;  g = nesterov ? g + momentum buf : buf;
+ *            p -= lr g.  momentum == 0: no buffer, state0 is not read.                       state0 = momentum_buffer
+ *   ADAM     g += wd p;  m = lerp(m, g, 1 - beta1);  v = beta2 v + (1 - beta2) g^2;
+ *            p -= (lr / bc1) m / (sqrt(v) / sqrt(bc2) + eps)                                 state0 = exp_avg, state1 = exp_avg_sq
+ *   ADAMAX   g += wd p;  m as ADAM;  u = max(beta2 u, |g| + eps);  p -= (lr / bc1) m / u      state0 = exp_avg, state1 = exp_inf
+ *   RMSPROP  g += wd p;  s = alpha s + (1 - alpha) g^2;  p -= lr g / (sqrt(s) + eps)          state0 = square_avg
+ * (g += wd p changes the local copy only: grad is never written.)  With has_clamp the new p is clamped to
+ * [clamp_min, clamp_max] in the same pass, the bits of Tensor.clamp_ afterwards.
+ * ---------------------------------------------------------------------------------- */
+#define VFI_OPTIM_SGD 0
+#define VFI_OPTIM_ADAM 1
+#define VFI_OPTIM_ADAMAX 2
+#define VFI_OPTIM_RMSPROP 3
+#define VFI_OPTIM_CHUNK 4096               /* elements one workgroup takes */
+#define VFI_OPTIM_TENSORS_PER_LAUNCH 40    /* both tables travel in the launch's 4 KiB of kernel arguments */
+#define VFI_OPTIM_CHUNKS_PER_LAUNCH 2048
+#define VFI_OPTIM_MAX_NUMEL (1LL << 40)    /* per tensor; element offsets are 64-bit */
+
+typedef struct vfi_optim_tensor {
+    float *param;       /* device, numel floats, 4-byte aligned; 16-byte accesses when all four pointers allow */
+    const float *grad;  /* device, read only */
+    float *state0;      /* see the table above; may be NULL where the kind does not use it */
+    float *state1;
+    long long numel;
+} vfi_optim_tensor;
+
+typedef struct vfi_optim_hyper {
+    double lr, beta1, beta2, alpha, eps, weight_decay, momentum, dampening;
+    double bias_correction1, bias_correction2; /* 1 - beta^step, from the step count in double (ADAM, ADAMAX) */
+    double clamp_min, clamp_max;
+    int nesterov, first_step, has_clamp;       /* first_step: SGD with momentum, the buffer is created (buf = g) */
+} vfi_optim_hyper;
+
+/* One update of `count` tensors that share `hyper` (HOST arrays, read before the call returns).  A workgroup takes one
+ * chunk of one tensor; a launch carries at most VFI_OPTIM_TENSORS_PER_LAUNCH tensors and VFI_OPTIM_CHUNKS_PER_LAUNCH chunks
+ * (a tensor may continue in the next launch), so the call is ceil(work / capacity) launches and nothing else: no device
+ * allocation, no copy, no wait.  The tensors must not overlap.
+ * Checked before anything touches a device: an unknown kind, count <= 0, null tensors or hyper, a record with a null param
+ * or grad, a null state the kind uses, or numel <= 0, and hyper-parameters outside torch's own ranges are
+ * VFI_ERR_INVALID_ARG; numel above VFI_OPTIM_MAX_NUMEL is VFI_ERR_UNSUPPORTED. */
+int vfi_optim_step(int kind, const vfi_optim_tensor *tensors, int count, const vfi_optim_hyper *hyper, vfi_stream_t stream);
+
+/* The limits above at run time (no device): elements per chunk, tensors and chunks per launch, the largest numel. */
+int vfi_optim_limits(long long *chunk, int *tensors_per_launch, int *chunks_per_launch, long long *max_numel);
+
 #ifdef __cplusplus
 }
 #endif

@@ -14,7 +14,11 @@ discriminator alone: forward, and backward to the input a
 modules (MIOpen) of the same layers, and the two linear kernels' bytes per second on the 512 (H/16)^2 -> 1024 layer.  When it
 has a `WGAN_GP` term (built with `gradient_penalty=True`) it prints the penalty pass split into the
 forward, the first backward and the second-order pass (with the two penalty kernels), next to the `create_graph` double
-backward of torch's own modules of the same layers."""
+backward of torch's own modules of the same layers.
+
+`--device-optimizer` (with `--loss`) times every trainer step a second time with `device_optimizer=True`: the network's and
+the discriminator's optimiser steps as one HIP pass each (vfi_amd.optim), all cases alternating over
+five rounds: median and min .. max of each."""
 import argparse
 import os
 import sys
@@ -57,23 +61,35 @@ def seeded_vgg16_state(seed=0):
     return sd
 
 
-def loss_section(net, f0, f1, f2, loss_string, vgg_weights, iters, warm):
+def loss_section(net, f0, f1, f2, loss_string, vgg_weights, iters, warm, device_optimizer=False):
     from vfi_amd.adacof import losses, utility
     from vfi_amd.adacof.losses import vgg
     weights = vgg_weights or seeded_vgg16_state()
-    opt_args = types.SimpleNamespace(optimizer="ADAMax", lr=1e-3, weight_decay=0)
     net.train(True)
-    for string in dict.fromkeys((DEFAULT_LOSS, loss_string)):
+    cases = [(string, False) for string in dict.fromkeys((DEFAULT_LOSS, loss_string))]
+    cases += [(string, True) for string, _ in cases] if device_optimizer else []
+    steps = []
+    for string, flag in cases:
+        opt_args = types.SimpleNamespace(optimizer="ADAMax", lr=1e-3, weight_decay=0, device_optimizer=flag)
         crit = losses.Loss(types.SimpleNamespace(loss=string, vgg_weights=weights, gpu_id=0, patch_size=f0.shape[2],
                                                  gradient_penalty="WGAN_GP" in string.replace("T_WGAN_GP", ""),
                                                  decay_type="step", lr_decay=20, gamma=0.5, **vars(opt_args)))
         opt = utility.make_optimizer(opt_args, net)
 
-        def step():
+        def step(crit=crit, opt=opt):
             opt.zero_grad()
             crit(net(f0, f2), f1, [f0, f2]).backward()
             opt.step()
-        print(f"  trainer step, --loss {string}: {timed(step, iters, warm):8.3f} ms")
+        steps.append((f"  trainer step{', device optimiser' if flag else ''}, --loss {string}", step))
+    rounds = 5 if device_optimizer else 1      # alternating, so that a difference can be read against the spread
+    ms = [[] for _ in steps]
+    for r in range(rounds):
+        for i, (_, step) in enumerate(steps):
+            ms[i].append(timed(step, iters, warm))
+    for (label, _), m in zip(steps, ms):
+        m.sort()
+        spread = f"  (median of {rounds}, {m[0]:.3f} .. {m[-1]:.3f})" if rounds > 1 else ""
+        print(f"{label}: {m[len(m) // 2]:8.3f} ms{spread}")
     if "GAN" in loss_string:
         discriminator_section(f0, iters, warm)
     if "WGAN_GP" in loss_string:
@@ -166,7 +182,7 @@ def gradient_penalty_section(f0, f1, iters, warm):
     net.train()
 
 
-def main(n=4, h=256, w=256, iters=10, warm=3, loss_string=None, vgg_weights=None):
+def main(n=4, h=256, w=256, iters=10, warm=3, loss_string=None, vgg_weights=None, device_optimizer=False):
     dev = torch.device("cuda:0")
     sd = nets_cpu.adacofnet_random_state_dict(0)
     net = AdaCoFNet(types.SimpleNamespace(kernel_size=5, dilation=1, gpu_id=0)).to(dev)
@@ -252,12 +268,14 @@ def main(n=4, h=256, w=256, iters=10, warm=3, loss_string=None, vgg_weights=None
 
     if loss_string:
         f1 = torch.rand((n, 3, h, w), generator=g).to(dev)
-        loss_section(net, f0, f1, f2, loss_string, vgg_weights, iters, warm)
+        loss_section(net, f0, f1, f2, loss_string, vgg_weights, iters, warm, device_optimizer)
 
 
 if __name__ == "__main__":
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("--loss", default=None, help="also time the trainer's step with this loss string")
     ap.add_argument("--vgg-weights", default=None, help="torchvision vgg16 state dict (default: seeded weights)")
+    ap.add_argument("--device-optimizer", action="store_true",
+                    help="with --loss: time each trainer step again with the optimisers of vfi_amd.optim (DESIGN.md section 29)")
     a = ap.parse_args()
-    main(loss_string=a.loss, vgg_weights=a.vgg_weights)
+    main(loss_string=a.loss, vgg_weights=a.vgg_weights, device_optimizer=a.device_optimizer)
