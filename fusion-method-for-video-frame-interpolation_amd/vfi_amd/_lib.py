@@ -131,6 +131,8 @@ SIGNATURES = {
     "vfi_avg_pool_backward": [c_f, c_f, c_i, c_i, c_i, c_i, c_s],
     "vfi_optim_step": [c_i, ctypes.c_void_p, c_i, ctypes.c_void_p, c_s],
     "vfi_optim_limits": [ctypes.POINTER(c_l), ctypes.POINTER(c_i), ctypes.POINTER(c_i), ctypes.POINTER(c_l)],
+    "vfi_yuv_to_rgb": [c_f, c_i, c_i, ctypes.c_void_p, c_f, c_f, c_f, c_s],
+    "vfi_rgb_to_yuv": [c_f, c_i, c_i, ctypes.c_void_p, c_f, c_s],
 }
 
 

@@ -92,6 +92,18 @@ class FusionInterpolator:
         f1, f2 = rgb_frame1.unsqueeze(0), rgb_frame2.unsqueeze(0)
         return self._run(rgb_frame1, rgb_frame2, output_baseline, pyr, phase_net, nlev, lab12, f1, f2)
 
+    @torch.no_grad()
+    def run_prepared(self, rgb_frame1, rgb_frame2, lab12, output_baseline=False):
+        """`__call__` for a caller that already holds the Lab planes: lab12 (6,H,W) = rgb2lab of both frames, as the clip
+        decoder writes them (ops.yuv_to_rgb).  lab12 is read, never written; it becomes FusionNet's `other` as is."""
+        h, w = rgb_frame1.shape[1:]
+        if tuple(lab12.shape) != (6, h, w) or tuple(rgb_frame2.shape) != (3, h, w):
+            raise ValueError(f"run_prepared: rgb frames must be (3, {h}, {w}) and lab12 (6, {h}, {w}), "
+                             f"got {tuple(rgb_frame2.shape)} and {tuple(lab12.shape)}")
+        pyr, phase_net = self._state(h, w)
+        return self._run(rgb_frame1, rgb_frame2, output_baseline, pyr, phase_net, pyr.height - 2, lab12,
+                         rgb_frame1.unsqueeze(0), rgb_frame2.unsqueeze(0))
+
     def _run(self, rgb_frame1, rgb_frame2, output_baseline, pyr, phase_net, nlev, lab12, f1, f2):
         h, w = rgb_frame1.shape[1:]
         # PhaseNet branch (:168-192)

@@ -1405,6 +1405,94 @@ def triplet_batch_prepare(src, params, size, rgb=True, lab=True):
     return rgb, lab
 
 
+YUV_420, YUV_444 = 0, 1                       # VFI_YUV_*: subsampling
+YUV_SITING_CENTRE, YUV_SITING_LEFT = 0, 1     # horizontal chroma siting
+YUV_BT709, YUV_BT601 = 0, 1                   # matrix
+YUV_LIMITED, YUV_FULL = 0, 1                  # range
+
+
+def yuv_frame_bytes(h, w, subsampling):
+    """Bytes of one frame: H * W luma, then two chroma planes."""
+    return h * w + 2 * ((h // 2) * (w // 2) if subsampling == YUV_420 else h * w)
+
+
+def _yuv_format(fmt, name):
+    """(ctypes int[4], subsampling) of a format: four integers (subsampling, siting, matrix, range), or an object whose
+    `.yuv` holds them (fusion_net.y4m.Y4MFormat).  The library checks the values."""
+    fmt = getattr(fmt, "yuv", fmt)
+    try:
+        vals = [int(v) for v in fmt]
+    except (TypeError, ValueError):
+        vals = None
+    if vals is None or len(vals) != 4:
+        raise VfiLibraryError(f"{name}: fmt must be four integers (subsampling, siting, matrix, range), got {fmt!r}")
+    return (ctypes.c_int * 4)(*vals), vals[0]
+
+
+def _yuv_frame(t, name, h, w, sub):
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        raise VfiLibraryError(f"{name}: frame must be a tensor on a HIP device (vfi_amd has no CPU path)")
+    if t.dtype != torch.uint8 or not t.is_contiguous() or t.numel() != yuv_frame_bytes(h, w, sub):
+        raise VfiLibraryError(f"{name}: frame must be dense uint8 with {yuv_frame_bytes(h, w, sub)} bytes for {h}x{w}, "
+                              f"got {t.dtype} {tuple(t.shape)}")
+    _lib.check_device(t, "frame")
+    return t.data_ptr()
+
+
+def _yuv_out(t, name, h, w, device):
+    """True = a new (3, h, w) tensor, None / False = not wanted, or a contiguous float32 (3, h, w) tensor to write into."""
+    if t is None or t is False:
+        return None
+    if t is True:
+        return torch.empty((3, h, w), dtype=torch.float32, device=device)
+    if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float32 or t.device != device \
+            or tuple(t.shape) != (3, h, w) or not t.is_contiguous():
+        raise VfiLibraryError(f"yuv_to_rgb: {name} must be a contiguous float32 tensor of shape (3, {h}, {w}) on {device}")
+    return t
+
+
+def yuv_to_rgb(frame, h, w, fmt, rgb=None, lab=(None, None)):
+    """One planar 8-bit Y'CbCr frame -> rgb in [0, 1] and its scaled Lab (vfi_yuv_to_rgb), in one launch on the current stream.
+    frame: dense uint8 on the device, any alignment, Y then Cb then Cr.  fmt: see _yuv_format.
+    rgb, lab[0], lab[1]: True = a new tensor, None / False = not wanted, or a (3, h, w) float32 tensor to write into (a
+    slice of a (6, h, w) Lab buffer); both Lab destinations get the same bits.  At least one must be wanted.
+    -> (rgb, lab[0], lab[1]), None where not wanted."""
+    h, w = int(h), int(w)
+    cfmt, sub = _yuv_format(fmt, "yuv_to_rgb")
+    if h <= 0 or w <= 0:
+        raise VfiLibraryError(f"yuv_to_rgb: bad size {h}x{w}")
+    fp = _yuv_frame(frame, "yuv_to_rgb", h, w, sub)
+    lab_a, lab_b = lab
+    rgb = _yuv_out(rgb, "rgb", h, w, frame.device)
+    lab_a, lab_b = _yuv_out(lab_a, "lab[0]", h, w, frame.device), _yuv_out(lab_b, "lab[1]", h, w, frame.device)
+    outs = [t.data_ptr() if t is not None else None for t in (rgb, lab_a, lab_b)]
+    moved = frame.numel() + 12 * h * w * sum(t is not None for t in (rgb, lab_a, lab_b))
+    _lib.call("vfi_yuv_to_rgb", fp, h, w, ctypes.addressof(cfmt), *outs, _lib.stream_ptr(),
+              work=("byte", float(moved), "yuv_to_rgb"))
+    return rgb, lab_a, lab_b
+
+
+def rgb_to_yuv(rgb, fmt, out=None):
+    """(3, H, W) float32 rgb (clamped to [0, 1] by the kernel) -> one planar 8-bit Y'CbCr frame (vfi_rgb_to_yuv), in one launch
+    on the current stream.  out: None (a new tensor) or a dense uint8 device tensor of the frame's size, any alignment."""
+    cfmt, sub = _yuv_format(fmt, "rgb_to_yuv")
+    if not isinstance(rgb, torch.Tensor) or not rgb.is_cuda:
+        raise VfiLibraryError("rgb_to_yuv: rgb must be a tensor on a HIP device (vfi_amd has no CPU path)")
+    if rgb.dim() != 3 or rgb.shape[0] != 3:
+        raise VfiLibraryError(f"rgb_to_yuv: rgb must be (3, H, W), got {tuple(rgb.shape)}")
+    h, w = rgb.shape[1:]
+    if sub == YUV_420 and (h % 2 or w % 2):
+        raise VfiLibraryError(f"rgb_to_yuv: 4:2:0 needs even sizes, got {h}x{w}")
+    if out is None:
+        out = torch.empty(yuv_frame_bytes(h, w, sub), dtype=torch.uint8, device=rgb.device)
+    op = _yuv_frame(out, "rgb_to_yuv", h, w, sub)
+    if out.device != rgb.device:
+        raise VfiLibraryError(f"rgb_to_yuv: out is on {out.device}, rgb on {rgb.device}")
+    _lib.call("vfi_rgb_to_yuv", _lib.dptr(rgb, "rgb"), h, w, ctypes.addressof(cfmt), op, _lib.stream_ptr(),
+              work=("byte", float(12 * h * w + out.numel()), "rgb_to_yuv"))
+    return out
+
+
 def optim_limits():
     """(elements per chunk, tensors per launch, chunks per launch, largest numel) of vfi_optim_step; needs no device."""
     c, m = ctypes.c_longlong(), ctypes.c_longlong()

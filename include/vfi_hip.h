@@ -999,6 +999,46 @@ int vfi_optim_step(int kind, const vfi_optim_tensor *tensors, int count, const v
 /* The limits above at run time (no device): elements per chunk, tensors and chunks per launch, the largest numel. */
 int vfi_optim_limits(long long *chunk, int *tensors_per_launch, int *chunks_per_launch, long long *max_numel);
 
+/* ------------------------------------------------------------------------------------
+ * Clip I/O: the frames of a YUV4MPEG2 stream to and from the tensors of the fused frame.  DESIGN.md section 30.
+ *   frame   DEVICE uint8, dense, any byte alignment, the stream's own layout: H * W luma bytes, then Cb, then Cr;
+ *           each chroma plane (H / 2) * (W / 2) bytes in 4:2:0 (H and W even), H * W bytes in 4:4:4 (any H, W >= 1)
+ *   format  HOST int[4] = (subsampling, horizontal chroma siting, matrix, range), the constants below; vertical siting is
+ *           always centre, the siting field is not used in 4:4:4 (but must hold one of its two values)
+ * With (Kr, Kb) = (0.2126, 0.0722) for BT.709 and (0.299, 0.114) for BT.601, Kg = 1 - Kr - Kb, and
+ * (y_off, y_scale, c_scale) = (16, 219, 224) for limited range (Y 16...235, C 16...240), (0, 255, 255) for full range.
+ * Both are single streaming launches: no workspace, no atomics, one writer per byte, the same bits on every call.
+ * Checked before anything is enqueued, nothing written: null pointers, H or W <= 0 and a format field that is none of its
+ * constants are VFI_ERR_INVALID_ARG; odd H or W in 4:2:0 is VFI_ERR_SHAPE; H * W >= 2^31 is VFI_ERR_UNSUPPORTED.
+ * ---------------------------------------------------------------------------------- */
+#define VFI_YUV_420 0
+#define VFI_YUV_444 1
+#define VFI_YUV_SITING_CENTRE 0 /* C420jpeg, C420paldv: chroma between luma columns 2i and 2i + 1 */
+#define VFI_YUV_SITING_LEFT 1   /* C420mpeg2, C420: chroma on luma column 2i */
+#define VFI_YUV_BT709 0
+#define VFI_YUV_BT601 1
+#define VFI_YUV_LIMITED 0
+#define VFI_YUV_FULL 1
+
+/* Decode.  rgb, lab_a, lab_b: (3, H, W) float32, 4-byte aligned (16-byte stores where a row segment allows), each may be
+ * NULL but not all three (VFI_ERR_INVALID_ARG); lab_a and lab_b receive the same bits (a frame is the second frame of one
+ * pair and the first of the next: it lands in two (6, H, W) Lab buffers from one read).  In float32:
+ *   y = (Y - y_off) / y_scale, cb = (Cb - 128) / c_scale, cr = (Cr - 128) / c_scale
+ *   R = y + 2 (1 - Kr) cr,  B = y + 2 (1 - Kb) cb,  G = (y - Kr R - Kb B) / Kg,  each then clamped to [0, 1]
+ *   lab = vfi_rgb2lab's formulas on the clamped rgb (its accuracy, not its bits)
+ * 4:2:0 chroma at luma pixel (r, x) is bilinear over the chroma bytes c, indices clamped to the plane: vertically, and
+ * horizontally for centre siting, even r takes c[r/2 - 1] / 4 + 3 c[r/2] / 4 and odd r takes 3 c[(r-1)/2] / 4 + c[(r+1)/2] / 4;
+ * for left siting even x takes c[x/2] and odd x takes (c[(x-1)/2] + c[(x+1)/2]) / 2. */
+int vfi_yuv_to_rgb(const unsigned char *frame, int H, int W, const int *format, float *rgb, float *lab_a, float *lab_b,
+                   vfi_stream_t stream);
+
+/* Encode.  rgb (3, H, W) float32, 4-byte aligned, clamped to [0, 1] first (torchvision.save_image's clamp).  At full
+ * resolution y = Kr R + Kg G + Kb B, cb = (B - y) / (2 (1 - Kb)), cr = (R - y) / (2 (1 - Kr)).  4:2:0 takes the mean of
+ * rows 2j and 2j + 1, then for centre siting the mean of columns 2i and 2i + 1, for left siting
+ * (c[2i - 1] + 2 c[2i] + c[2i + 1]) / 4 with the column index clamped.  Y = y_off + y_scale y, C = 128 + c_scale c, then
+ * floor(v + 0.5), then the clamp to the range's limits.  A NaN in rgb gives the lower limit in every byte it reaches. */
+int vfi_rgb_to_yuv(const float *rgb, int H, int W, const int *format, unsigned char *frame, vfi_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
