@@ -133,6 +133,8 @@ SIGNATURES = {
     "vfi_optim_limits": [ctypes.POINTER(c_l), ctypes.POINTER(c_i), ctypes.POINTER(c_i), ctypes.POINTER(c_l)],
     "vfi_yuv_to_rgb": [c_f, c_i, c_i, ctypes.c_void_p, c_f, c_f, c_f, c_s],
     "vfi_rgb_to_yuv": [c_f, c_i, c_i, ctypes.c_void_p, c_f, c_s],
+    "vfi_luma_sad": [c_f, c_f, c_l, c_f, c_s],
+    "vfi_frame_pick": [c_f, c_f, c_l, c_f, c_f, ctypes.c_ulonglong, c_f, c_s],
 }
 
 

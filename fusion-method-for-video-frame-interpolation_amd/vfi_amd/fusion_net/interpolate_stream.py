@@ -18,6 +18,13 @@ bytes with one `readinto` and one `write`, and everything between those bytes an
 
 n input frames give 2n - 1 output frames; the output header is the input's with F doubled (unless `keep_rate`).  A stream is
 not sharded over GPUs.  H and W must be multiples of 8 (FusionNet's three 2x poolings).
+
+Two options, both off by default, and off is the loop above launch for launch:
+  * `--factor 4 | 8`: a pair's factor - 1 frames come from FusionInterpolator.run_recursive on that pair's stream and
+    runner, each with its own rgb_to_yuv, D2H copy and event; n frames give factor (n - 1) + 1, F is multiplied by factor;
+  * `--scene_threshold T`: one ops.luma_sad per pair on the two frames' device bytes and one ops.frame_pick per encoded
+    frame, which on a cut replaces it by the nearer original's bytes.  The statistic and the decision stay on the
+    device; the flag comes back with the pair's first frame and is read by the writer thread (`args.scene_cuts`).
 """
 import argparse
 import os
@@ -25,7 +32,7 @@ import queue
 import sys
 import threading
 
-from . import y4m
+from . import scene, y4m
 
 
 def _check_size(fmt):
@@ -36,11 +43,16 @@ def _check_size(fmt):
 
 def interpolate_stream(args, src, dst, runners=None, frames_in_flight=2):
     """Interpolates every consecutive pair of the Y4M stream `src` (binary, readable) into `dst` (binary, writable).
-    args: gpu_id, matrix ('bt709' | 'bt601'), range ('limited' | 'full'), keep_rate, and the model fields of build_models
-    when `runners` is None.  Returns the number of interpolated frames; `args.truncated` tells whether the input stopped
-    inside a frame (the complete frames are still finished and flushed)."""
+    args: gpu_id, matrix ('bt709' | 'bt601'), range ('limited' | 'full'), keep_rate, factor (2 | 4 | 8, default 2),
+    scene_threshold (percent, default None = off), and the model fields of build_models when `runners` is None.
+    Returns the number of interpolated frames; `args.truncated` tells whether the input stopped inside a frame (the
+    complete frames are still finished and flushed), `args.scene_cuts` lists the source pairs flagged as cuts."""
+    factor, threshold = getattr(args, "factor", 2), getattr(args, "scene_threshold", None)
+    if factor not in (2, 4, 8):
+        raise ValueError(f"interpolate_stream: factor must be 2, 4 or 8, got {factor!r}")
     fmt = y4m.read_header(src, getattr(args, "matrix", "bt709"), getattr(args, "range", "limited"))
     _check_size(fmt)                                       # before the first launch, before a byte is written
+    cut_sad = None if threshold is None else scene.min_sad(threshold, fmt.width * fmt.height)
     import torch
     from .. import ops
     from .interpolate_twoframe import FusionInterpolator, build_models
@@ -51,14 +63,18 @@ def interpolate_stream(args, src, dst, runners=None, frames_in_flight=2):
         pn = getattr(args, "phase_net_checkpoint", "./src/phase_net/phase_net.pt")
         state = torch.load(pn, map_location="cpu") if pn and os.path.exists(pn) else None
         runners = [FusionInterpolator(adacof, fusion, state, device) for _ in range(max(1, frames_in_flight))]
-    rate = fmt.rate if getattr(args, "keep_rate", False) or fmt.rate is None else (fmt.rate[0] * 2, fmt.rate[1])
+    rate = fmt.rate if getattr(args, "keep_rate", False) or fmt.rate is None else (fmt.rate[0] * factor, fmt.rate[1])
     y4m.write_header(dst, fmt, rate)
 
     h, w, nbytes = fmt.height, fmt.width, fmt.frame_bytes
-    n_in, n_out = 2 * max(1, frames_in_flight) + 2, max(1, frames_in_flight) + 1
+    n_in, n_out = 2 * max(1, frames_in_flight) + 2, (max(1, frames_in_flight) + 1) * (factor - 1)
     ring = [torch.empty(nbytes, dtype=torch.uint8, pin_memory=True) for _ in range(n_in)]
     out_ring = [torch.empty(nbytes, dtype=torch.uint8, pin_memory=True) for _ in range(n_out)]
     ring_np, out_np = [t.numpy() for t in ring], [t.numpy() for t in out_ring]
+    cuts = []                                              # pairs flagged on the device, appended by the writer in order
+    if cut_sad is not None:                                # a pair's flag lands next to its first frame's bytes
+        out_flag = torch.zeros(n_out, dtype=torch.int32, pin_memory=True)
+        out_flag_np = out_flag.numpy()
     free, out_free, filled, to_write = queue.Queue(), queue.Queue(), queue.Queue(), queue.Queue()
     for i in range(n_in):
         free.put(i)
@@ -88,7 +104,7 @@ def interpolate_stream(args, src, dst, runners=None, frames_in_flight=2):
             item = to_write.get()
             if item is None:
                 break
-            kind, slot, line, event = item
+            kind, slot, line, event, flagged = item
             try:
                 if kind == "original":                     # the slot's own bytes; then wait for its H2D copy and hand it back
                     if not failed:
@@ -96,6 +112,8 @@ def interpolate_stream(args, src, dst, runners=None, frames_in_flight=2):
                     event.synchronize()
                 else:                                      # the D2H copy of this frame has landed in its pinned buffer
                     event.synchronize()
+                    if flagged is not None and out_flag_np[slot]:      # (the pair's flag came with its first frame)
+                        cuts.append(flagged)
                     if not failed:
                         y4m.write_frame(dst, line, out_np[slot])
             except BaseException as e:                     # noqa: BLE001 (keep draining: the other threads wait on the slots)
@@ -110,7 +128,9 @@ def interpolate_stream(args, src, dst, runners=None, frames_in_flight=2):
     for t in threads:
         t.start()
     streams = [torch.cuda.Stream(device=device) for _ in runners]
-    prev = None                                            # (rgb, lab12 with its first half filled, decode event) of frame k - 1
+    # of frame k - 1: (rgb, lab12 with its first half filled, decode event, its bytes on the device, the SAD word of the pair
+    # it closed); the last two are read only with a scene threshold
+    prev = None
     k = written = 0
     try:
         while True:
@@ -120,7 +140,8 @@ def interpolate_stream(args, src, dst, runners=None, frames_in_flight=2):
             slot, line = item
             pair = max(k - 1, 0)                           # frame k closes pair k - 1 and is uploaded on that pair's stream
             s, runner = streams[pair % len(runners)], runners[pair % len(runners)]
-            oslot = out_free.get() if prev is not None else None
+            oslots = [out_free.get() for _ in range(factor - 1)] if prev is not None else []
+            done, sad = [], None
             with torch.cuda.stream(s):
                 frame = torch.empty(nbytes, dtype=torch.uint8, device=device)
                 frame.copy_(ring[slot], non_blocking=True)
@@ -133,19 +154,31 @@ def interpolate_stream(args, src, dst, runners=None, frames_in_flight=2):
                     prev[0].record_stream(s)
                     prev[1].record_stream(s)
                 ops.yuv_to_rgb(frame, h, w, fmt, rgb=rgb, lab=(lab12[:3], prev[1][3:] if prev is not None else None))
+                if cut_sad is not None and prev is not None:   # both frames' bytes are on the device; before `up`, so that
+                    prev[3].record_stream(s)                   # the next pair's wait covers this word too
+                    sad = ops.luma_sad(prev[3], frame, h * w)
                 up = torch.cuda.Event()
                 up.record(s)                               # the next pair waits for this, not for this pair's compute
                 if prev is not None:
-                    final = runner.run_prepared(prev[0], rgb, prev[1])["final"][0]
-                    enc = ops.rgb_to_yuv(final, fmt)
-                    out_ring[oslot].copy_(enc, non_blocking=True)
-                    d2h = torch.cuda.Event()
-                    d2h.record(s)
-            if prev is not None:
-                to_write.put(("interpolated", oslot, b"FRAME\n", d2h))
+                    finals = runner.run_recursive(prev[0], rgb, prev[1], factor)
+                    for j, (final, oslot) in enumerate(zip(finals, oslots), 1):      # the frame at t = j / factor
+                        enc = ops.rgb_to_yuv(final, fmt)
+                        if sad is not None:                # on a cut: the nearer original's bytes (the first at t = 1/2)
+                            if prev[4] is not None:
+                                prev[4].record_stream(s)
+                            flag = torch.empty(1, dtype=torch.int32, device=device) if j == 1 else None
+                            ops.frame_pick(enc, prev[3] if 2 * j <= factor else frame, sad, prev[4], cut_sad, cut=flag)
+                            if flag is not None:
+                                out_flag[oslot:oslot + 1].copy_(flag, non_blocking=True)
+                        out_ring[oslot].copy_(enc, non_blocking=True)
+                        d2h = torch.cuda.Event()
+                        d2h.record(s)
+                        done.append(d2h)
+            for j, (oslot, d2h) in enumerate(zip(oslots, done)):
+                to_write.put(("interpolated", oslot, b"FRAME\n", d2h, pair if sad is not None and j == 0 else None))
                 written += 1
-            to_write.put(("original", slot, line, h2d))
-            prev = (rgb, lab12, up)
+            to_write.put(("original", slot, line, h2d, None))
+            prev = (rgb, lab12, up, frame, sad)
             k += 1
     except BaseException as e:                             # noqa: BLE001
         errors.insert(0, e)
@@ -160,6 +193,7 @@ def interpolate_stream(args, src, dst, runners=None, frames_in_flight=2):
     threads[0].join()
     dst.flush()
     args.truncated = bool(fmt.truncated)
+    args.scene_cuts = cuts
     return written
 
 
@@ -180,6 +214,13 @@ parser.add_argument("--range", type=str, choices=sorted(y4m.RANGES), default="li
                     help="the header's XCOLORRANGE token wins over this")
 parser.add_argument("--keep_rate", action="store_true", help="leave the header's F token alone (slow motion)")
 parser.add_argument("--frames_in_flight", type=int, default=2)
+parser.add_argument("--factor", type=int, choices=(2, 4, 8), default=2,
+                    help="frame-rate multiple: 4 and 8 interpolate between an original and an interpolated frame")
+parser.add_argument("--scene_threshold", type=float, default=None,
+                    help="off by default.  Percent of the luma range: a pair whose mean absolute luma difference m gives "
+                         "min(m, |m - m of the previous pair|) >= this is a scene cut, and the nearer original is repeated "
+                         "in place of its interpolated frames.  ffmpeg's scdet filter documents this rule with a default of "
+                         "10, a starting point; no footage was used to tune anything here")
 
 
 def main(argv=None):
@@ -198,7 +239,8 @@ def main(argv=None):
         src = os.fdopen(os.dup(0), "rb") if args.input == "-" else open(args.input, "rb")
         done = interpolate_stream(args, src, dst, frames_in_flight=args.frames_in_flight)
         dst.flush()
-        print(f"interpolate_stream: {done} interpolated frames", file=sys.stderr)
+        cuts = "" if args.scene_threshold is None else f", {len(args.scene_cuts)} scene cuts"
+        print(f"interpolate_stream: {done} interpolated frames{cuts}", file=sys.stderr)
         if args.truncated:
             print("interpolate_stream: warning: the input stopped inside a frame; the complete frames were written",
                   file=sys.stderr)

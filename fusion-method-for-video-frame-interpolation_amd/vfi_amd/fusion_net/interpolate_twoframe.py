@@ -104,7 +104,31 @@ class FusionInterpolator:
         return self._run(rgb_frame1, rgb_frame2, output_baseline, pyr, phase_net, pyr.height - 2, lab12,
                          rgb_frame1.unsqueeze(0), rgb_frame2.unsqueeze(0))
 
+    @torch.no_grad()
+    def run_recursive(self, rgb_frame1, rgb_frame2, lab12, factor):
+        """The factor - 1 frames between two frames, in time order, each (3,H,W): t = 1/factor ... (factor - 1)/factor.
+        The networks predict the midpoint only, so factor 4 and 8 recurse: the midpoint, then the midpoints of (first,
+        midpoint) and (midpoint, second).  Arguments as run_prepared; factor 2 is run_prepared and nothing else.
+        A result that becomes an input is clamped to [0, 1] as the clip decoder clamps its rgb, and its Lab planes come
+        from ops.rgb2lab, written into the (6,H,W) buffers of the two pairs it belongs to; an original's Lab planes are
+        copied there, not computed again.  The returned frames are the networks' own output (`final`), float32."""
+        if factor not in (2, 4, 8):
+            raise ValueError(f"run_recursive: factor must be 2, 4 or 8, got {factor!r}")
+        mid = self.run_prepared(rgb_frame1, rgb_frame2, lab12)["final"][0]      # a tensor of its own: see _run
+        if factor == 2:
+            return [mid]
+        m = mid.clamp(0.0, 1.0)
+        left, right = torch.empty_like(lab12), torch.empty_like(lab12)
+        left[:3].copy_(lab12[:3])
+        right[3:].copy_(lab12[3:])
+        ops.rgb2lab(m, out=left[3:])
+        ops.rgb2lab(m, out=right[:3])
+        return (self.run_recursive(rgb_frame1, m, left, factor // 2) + [mid] +
+                self.run_recursive(m, rgb_frame2, right, factor // 2))
+
     def _run(self, rgb_frame1, rgb_frame2, output_baseline, pyr, phase_net, nlev, lab12, f1, f2):
+        """`final` is a tensor of its own (FusionNet's head, ops.tanh_residual_clamp, allocates its output), not a view into
+        the runner's per-size state: it survives later calls on the same runner, so run_recursive needs no clone."""
         h, w = rgb_frame1.shape[1:]
         # PhaseNet branch (:168-192)
         vals, bufs, amp_max = pyr.filter(lab12, concat_frames=2, phase_scale=1.0 / math.pi,

@@ -1493,6 +1493,66 @@ def rgb_to_yuv(rgb, fmt, out=None):
     return out
 
 
+def _scene_bytes(t, name, who, least):
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        raise VfiLibraryError(f"{who}: {name} must be a tensor on a HIP device (vfi_amd has no CPU path)")
+    if t.dtype != torch.uint8 or not t.is_contiguous() or t.numel() < least:
+        raise VfiLibraryError(f"{who}: {name} must be dense uint8 with at least {least} bytes, got {t.dtype} {tuple(t.shape)}")
+    _lib.check_device(t, name)
+    return t.data_ptr()
+
+
+def _scene_word(t, name, who, dtype, device):
+    """One device word of `dtype` (None -> NULL)."""
+    if t is None:
+        return None
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        raise VfiLibraryError(f"{who}: {name} must be a tensor on a HIP device (vfi_amd has no CPU path)")
+    if t.dtype != dtype or t.numel() != 1 or t.device != device:
+        raise VfiLibraryError(f"{who}: {name} must be one {dtype} element on {device}, got {t.dtype} {tuple(t.shape)} on {t.device}")
+    return t.data_ptr()
+
+
+def luma_sad(frame_a, frame_b, n, out=None):
+    """Sum of |a[i] - b[i]| over the first n bytes of two dense uint8 device tensors (vfi_luma_sad; two frames and n = H * W
+    give the luma planes), exact, in launches on the current stream.  -> `out`, a one-element int64 device tensor (a new
+    one for None; what it held before does not matter).  Nothing comes back to the host."""
+    n = int(n)
+    if n <= 0:
+        raise VfiLibraryError(f"luma_sad: bad size {n}")
+    pa, pb = _scene_bytes(frame_a, "frame_a", "luma_sad", n), _scene_bytes(frame_b, "frame_b", "luma_sad", n)
+    if frame_a.device != frame_b.device:
+        raise VfiLibraryError(f"luma_sad: frame_a is on {frame_a.device}, frame_b on {frame_b.device}")
+    if out is None:
+        out = torch.empty(1, dtype=torch.int64, device=frame_a.device)
+    _lib.call("vfi_luma_sad", pa, pb, n, _scene_word(out, "out", "luma_sad", torch.int64, frame_a.device), _lib.stream_ptr(),
+              work=("byte", float(2 * n), "luma_sad"))
+    return out
+
+
+def frame_pick(dst, src, sad, sad_prev, min_sad, cut=None):
+    """Scene-cut decision and replacement on the device (vfi_frame_pick), one launch on the current stream: with
+    p = sad_prev (0 for None) the pair is a cut when min(sad, |sad - p|) >= min_sad (fusion_net.scene.min_sad turns a
+    threshold into it); on a cut dst's bytes become src's, otherwise dst is left alone.  dst, src: dense uint8 device
+    tensors of one size; sad, sad_prev: one-element int64 device tensors as luma_sad returns them; cut: a one-element int32
+    device tensor that receives 1 or 0, or None.  -> cut."""
+    min_sad = int(min_sad)
+    if not 0 <= min_sad < 1 << 64:
+        raise VfiLibraryError(f"frame_pick: min_sad {min_sad} is not an unsigned 64-bit value")
+    pd = _scene_bytes(dst, "dst", "frame_pick", 1)
+    ps = _scene_bytes(src, "src", "frame_pick", dst.numel())
+    if src.numel() != dst.numel() or src.device != dst.device:
+        raise VfiLibraryError(f"frame_pick: src must have dst's {dst.numel()} bytes on {dst.device}, "
+                              f"got {src.numel()} on {src.device}")
+    if sad is None:
+        raise VfiLibraryError("frame_pick: sad must be a one-element int64 device tensor")
+    words = [_scene_word(sad, "sad", "frame_pick", torch.int64, dst.device),
+             _scene_word(sad_prev, "sad_prev", "frame_pick", torch.int64, dst.device)]
+    _lib.call("vfi_frame_pick", pd, ps, dst.numel(), *words, min_sad, _scene_word(cut, "cut", "frame_pick", torch.int32, dst.device),
+              _lib.stream_ptr(), work=("byte", float(2 * dst.numel()), "frame_pick"))
+    return cut
+
+
 def optim_limits():
     """(elements per chunk, tensors per launch, chunks per launch, largest numel) of vfi_optim_step; needs no device."""
     c, m = ctypes.c_longlong(), ctypes.c_longlong()

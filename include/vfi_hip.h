@@ -1039,6 +1039,27 @@ int vfi_yuv_to_rgb(const unsigned char *frame, int H, int W, const int *format, 
  * floor(v + 0.5), then the clamp to the range's limits.  A NaN in rgb gives the lower limit in every byte it reaches. */
 int vfi_rgb_to_yuv(const float *rgb, int H, int W, const int *format, unsigned char *frame, vfi_stream_t stream);
 
+/* Scene cuts, decided on the device: the statistic and the decision stay in device words, so the
+ * thread that enqueues a clip never waits for either.  Both calls check before anything is enqueued, nothing written: a
+ * null pointer (except where NULL is allowed below) or a size <= 0 is VFI_ERR_INVALID_ARG, a size >= 2^31 is
+ * VFI_ERR_UNSUPPORTED.
+ *
+ * Sum of absolute differences: *sad = sum over i < n of |a[i] - b[i]|, exact.  a, b: DEVICE bytes of any alignment,
+ * independent of each other (the clip loop passes two frames and n = H * W, the luma plane); sad: one DEVICE 64-bit word,
+ * 8-byte aligned.  What *sad held before does not matter: the call zeroes it on `stream`, then each workgroup adds one
+ * 64-bit integer to it, so every call gives the same bits. */
+int vfi_luma_sad(const unsigned char *a, const unsigned char *b, long long n, unsigned long long *sad, vfi_stream_t stream);
+
+/* With p = sad_prev ? *sad_prev : 0 and s = min(*sad, |*sad - p|) (the difference without unsigned wrap), the pair is a
+ * cut when s >= min_sad; min_sad = 0 always is.  On a cut dst[0, nbytes) = src[0, nbytes); otherwise dst is not written.
+ * cut (one DEVICE int, may be NULL) receives 1 or 0 either way.  dst, src: DEVICE bytes of any alignment, independent of
+ * each other, not overlapping; sad, sad_prev: DEVICE 64-bit words as vfi_luma_sad writes them, sad_prev may be NULL.
+ * This is the rule ffmpeg's scdet filter documents, in integers: with the mean absolute luma difference in percent
+ * m = 100 sad / (255 n), the score is min(m, |m - m_prev|) (m_prev = 0 for the first pair) and a cut is score >= threshold;
+ * the host passes min_sad = ceil(threshold * 255 * n / 100). */
+int vfi_frame_pick(unsigned char *dst, const unsigned char *src, long long nbytes, const unsigned long long *sad,
+                   const unsigned long long *sad_prev, unsigned long long min_sad, int *cut, vfi_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

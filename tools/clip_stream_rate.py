@@ -1,9 +1,10 @@
 #!/usr/bin/env python3
 """Y4M-inclusive clip rate at 1080p (read + H2D + decode + interpolate + encode + D2H + write), the counterpart of
-clip_io_rate.py for vfi_amd.fusion_net.interpolate_stream.  With --kernels also the two conversion
-kernels alone: time per call and effective TB/s over the bytes they move.
+clip_io_rate.py for vfi_amd.fusion_net.interpolate_stream (DESIGN.md sections 30 and 31).  With --kernels instead the
+conversion and scene-cut kernels alone: time per call and effective TB/s over the bytes they move.
 
-usage: clip_stream_rate.py [frames=13] [frames_in_flight=2] [--kernels]"""
+usage: clip_stream_rate.py [frames=13] [frames_in_flight=2] [--factor 2|4|8] [--scene_threshold T] [--kernels]"""
+import argparse
 import os
 import sys
 import tempfile
@@ -19,9 +20,14 @@ from vfi_amd import ops  # noqa: E402
 from vfi_amd.fusion_net import interpolate_stream as st  # noqa: E402
 
 H, W = 1080, 1920
-argv = [a for a in sys.argv[1:] if not a.startswith("--")]
-n = int(argv[0]) if len(argv) > 0 else 13
-fif = int(argv[1]) if len(argv) > 1 else 2
+ap = argparse.ArgumentParser()
+ap.add_argument("frames", type=int, nargs="?", default=13)
+ap.add_argument("frames_in_flight", type=int, nargs="?", default=2)
+ap.add_argument("--factor", type=int, choices=(2, 4, 8), default=2)
+ap.add_argument("--scene_threshold", type=float, default=None)
+ap.add_argument("--kernels", action="store_true")
+opts = ap.parse_args()
+n, fif = opts.frames, opts.frames_in_flight
 dev = torch.device("cuda:0")
 fmt = (ops.YUV_420, ops.YUV_SITING_CENTRE, ops.YUV_BT709, ops.YUV_LIMITED)
 
@@ -38,7 +44,7 @@ def timed(fn, reps=50, warm=5):
     return e0.elapsed_time(e1) / reps * 1e-3
 
 
-if "--kernels" in sys.argv:
+if opts.kernels:
     # rotate over enough buffers that no call finds its bytes in the 256 MiB Infinity Cache
     sets = 24
     rgbs = [torch.rand((3, H, W), device=dev) for _ in range(sets)]
@@ -59,6 +65,17 @@ if "--kernels" in sys.argv:
         sec = timed(lambda: fn(nxt()))
         moved = nb + outs * plane
         print(f"  {name:24s} {W}x{H} 4:2:0  {sec * 1e6:7.1f} us  {moved / 1e6:6.1f} MB  {moved / sec * 1e-12:5.2f} TB/s")
+    # the scene-cut calls: the statistic over two luma planes, and the pick with and without a cut (a cut copies the frame).
+    # They touch the 24 frames only, 75 MB, which stay in the Infinity Cache -- as in the clip loop, where both calls read
+    # bytes that were uploaded or encoded just before.  luma_sad's time includes its 8-byte memset.
+    words = [torch.zeros(1, dtype=torch.int64, device=dev) for _ in range(sets)]
+    big = torch.full((1,), 1 << 40, dtype=torch.int64, device=dev)
+    for name, moved, fn in (
+            ("luma_sad", 2 * H * W, lambda i: ops.luma_sad(frames[i], frames[(i + 1) % sets], H * W, out=words[i])),
+            ("frame_pick, no cut", 16, lambda i: ops.frame_pick(frames[i], frames[(i + 1) % sets], words[i], None, 1 << 50)),
+            ("frame_pick, cut", 2 * nb, lambda i: ops.frame_pick(frames[i], frames[(i + 1) % sets], big, None, 1))):
+        sec = timed(lambda: fn(nxt()))
+        print(f"  {name:24s} {W}x{H} 4:2:0  {sec * 1e6:7.1f} us  {moved / 1e6:6.1f} MB  {moved / sec * 1e-12:5.2f} TB/s")
     # a plain device copy of the decoder's largest traffic (read + write counted), as the yardstick of the same run
     bufs = [(torch.empty(3 * plane // 8, device=dev), torch.empty(3 * plane // 8, device=dev)) for _ in range(sets)]
     sec = timed(lambda: (lambda p: p[1].copy_(p[0]))(bufs[nxt()]))
@@ -75,7 +92,8 @@ with tempfile.TemporaryDirectory() as td:
         for i in range(n):
             f.write(b"FRAME\n")
             f.write(ops.rgb_to_yuv(torch.roll(base, 3 * i, dims=2), fmt).cpu().numpy().tobytes())
-    args = types.SimpleNamespace(gpu_id=0, matrix="bt709", range="limited", keep_rate=False)
+    args = types.SimpleNamespace(gpu_id=0, matrix="bt709", range="limited", keep_rate=False, factor=opts.factor,
+                                 scene_threshold=opts.scene_threshold)
 
     def run():
         with open(path, "rb") as s, open(out, "wb") as d:
@@ -84,6 +102,12 @@ with tempfile.TemporaryDirectory() as td:
     t0 = time.perf_counter()
     done = run()
     dt = time.perf_counter() - t0
-    assert os.path.getsize(out) > (2 * n - 1) * W * H * 3 // 2
+    frames_out = opts.factor * (n - 1) + 1
+    assert os.path.getsize(out) > frames_out * W * H * 3 // 2
+    extra = ""
+    if opts.factor != 2 or opts.scene_threshold is not None:
+        extra = f", factor {opts.factor}, {frames_out / dt:.2f} output frames/s"
+    if opts.scene_threshold is not None:
+        extra += f", threshold {opts.scene_threshold:g}: {len(args.scene_cuts)} scene cuts"
     print(f"clip of {n} frames at {W}x{H} from/to Y4M: {done} interpolated frames in {dt:.2f} s = {done / dt:.2f} frames/s "
-          f"({fif} frames in flight)")
+          f"({fif} frames in flight{extra})")
