@@ -123,6 +123,7 @@ SIGNATURES = {
     "vfi_l1_forward": [c_f, c_f, c_l, c_i, c_fl, c_f, c_f, c_s],
     "vfi_l1_backward": [c_f] * 5 + [c_l, c_i, c_fl, c_s],
     "vfi_triplet_batch_prepare": [c_f, ctypes.c_void_p, c_f, c_l, c_l, c_f, c_l, c_l] + [c_i] * 5 + [c_s],
+    "vfi_yuv_triplet_batch_prepare": [c_f, c_l, ctypes.c_void_p, ctypes.c_void_p, c_f, c_l, c_l, c_f, c_l, c_l] + [c_i] * 5 + [c_s],
     "vfi_lpips_head_forward": [c_f, c_l, c_f, c_l] + [c_f] * 4 + [c_i] * 3 + [c_s],
     "vfi_lpips_head_backward": [c_f, c_l, c_f, c_l, c_f, c_f, c_f, c_l, c_f, c_l] + [c_i] * 4 + [c_s],
     "vfi_lpips_normalize": [c_f, c_l, c_f, c_l, c_i, c_i, c_i, c_s],

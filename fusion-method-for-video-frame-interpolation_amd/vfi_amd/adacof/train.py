@@ -5,6 +5,8 @@ The reference's flags and defaults, plus `--vgg_weights` (a torchvision vgg16 st
 default: the environment variable VFI_VGG16_WEIGHTS), `--lpips_weights` (the head weights of an `LPIPS` term, which reads
 `--vgg_weights` too; default: VFI_LPIPS_WEIGHTS), `--workers` (decoding threads of TripletLoader) and `--gradient_penalty`
 (builds the `WGAN_GP` type of `--loss`, e.g. `--gradient_penalty --loss 1*Charb+0.005*WGAN_GP`; without it that type raises).
+`--train_clips DIR` (with `--clip_stride`, `--matrix`, `--range`) trains from the `*.y4m` clips of DIR instead of `--train`,
+with `--patch_size` as the crop (train/clipreader.py).
 
 Differences from the reference:
 
@@ -20,7 +22,7 @@ import os
 import torch
 
 from . import losses
-from .datareader import DBreader_Vimeo90k, TripletLoader
+from ..train import clipreader
 from .models import Model
 from .TestModule import Middlebury_other
 from .trainer import Trainer
@@ -40,6 +42,7 @@ parser.add_argument('--out_dir', type=str, default='./output_adacof_train')
 parser.add_argument('--load', type=str, default=None)
 parser.add_argument('--test_input', type=str, default='./test_input/middlebury_others/input')
 parser.add_argument('--gt', type=str, default='./test_input/middlebury_others/gt')
+clipreader.add_arguments(parser)       # --train_clips PATH [--clip_stride N --matrix M --range R]: train from .y4m clips
 
 # Learning Options
 parser.add_argument('--epochs', type=int, default=50, help='Max Epochs')
@@ -74,9 +77,8 @@ def main(argv=None):
     if '.' not in args.model:
         args.model = 'vfi_amd.adacof.models.' + args.model
 
-    dataset = DBreader_Vimeo90k(args.train, random_crop=(args.patch_size, args.patch_size))
+    dataset, train_loader = clipreader.training_input(args, (args.patch_size, args.patch_size), device, rgb=True, lab=False)
     TestDB = Middlebury_other(args.test_input, args.gt, device=device)
-    train_loader = TripletLoader(dataset, args.batch_size, shuffle=True, workers=args.workers, device=device, rgb=True, lab=False)
     model = Model(args)
     loss = losses.Loss(args)
 

@@ -5,7 +5,8 @@ The reference's flags and defaults, plus `--out_dir` (default: the reference's `
 `--crop H W` (256 256), `--height` (12), `--workers`, `--phasenet_checkpoint`, `--adacof_checkpoint` (defaults: the
 reference's paths), `--test_paths A B C`, and `--lpips_weight` (0) with `--vgg_weights` / `--lpips_weights` (defaults: the
 environment variables VFI_VGG16_WEIGHTS / VFI_LPIPS_WEIGHTS) for the perceptual term of trainer.py, and `--ssim_weight` (0) for
-its structural term (evaluation/ssim.py; no weights file).  `--save` is accepted and raises NotImplementedError (trainer.py).
+its structural term (evaluation/ssim.py; no weights file).  `--train_clips DIR` (with `--clip_stride`, `--matrix`, `--range`)
+trains from the `*.y4m` clips of DIR instead of `--train` (train/clipreader.py).  `--save` is accepted and raises NotImplementedError (trainer.py).
 
 The network is `FusionNet(kernel, pad, dil)` with its default three uncertainty maps, which `Trainer.predict` feeds it; the
 reference's script builds `FusionNet(uncertainty_maps=0)` (train.py:79), whose first convolution has three input channels
@@ -18,7 +19,7 @@ import numpy as np
 import torch
 
 from ..phase_net.phase_net import PhaseNet
-from ..train.datareader import DBreader_Vimeo90k, TripletLoader
+from ..train import clipreader
 from ..train.pyramid import Pyramid
 from ..train.train import finish, write_config
 from ..train.trainer import ADACOF_CHECKPOINT, load_adacof
@@ -34,6 +35,7 @@ parser.add_argument('--gpu_id', type=int, default=1)
 parser.add_argument('--train', type=str, default='./Trainset/vimeo/vimeo_triplet')
 parser.add_argument('--load', type=str, default=None)
 parser.add_argument('--out_dir', type=str, default=None)
+clipreader.add_arguments(parser)       # --train_clips PATH [--clip_stride N --matrix M --range R]: train from .y4m clips
 
 # Learning Options
 parser.add_argument('--epochs', type=int, default=1, help='max epochs')
@@ -85,8 +87,7 @@ def main(argv=None):
     torch.manual_seed(args.seed)
 
     device = torch.device(f'cuda:{args.gpu_id}')
-    dataset = DBreader_Vimeo90k(args.train, random_crop=tuple(args.crop))
-    train_loader = TripletLoader(dataset, args.batch_size, shuffle=True, workers=args.workers, device=device)
+    dataset, train_loader = clipreader.training_input(args, tuple(args.crop), device)
 
     pyr = Pyramid(height=args.height, nbands=4, scale_factor=np.sqrt(2), device=device)
     fusion_net = FusionNet(kernel=args.kernel, pad=args.pad, dil=args.dilation).to(device)

@@ -191,6 +191,42 @@ def read_frame_into(stream, buf, fmt=None):
     return line
 
 
+def index_clip(path, matrix="bt709", range="limited"):
+    """Random access to a clip on disk -> (Y4MFormat, offsets): the byte offset of each complete frame's data.  `path` is a
+    file name or a seekable binary stream.  The FRAME lines are walked with seeks (a FRAME line may carry parameters, so
+    frames are not equidistant in general); no frame data is read.  A last frame that stops short -- in its line or in its
+    bytes -- is left out and sets `fmt.truncated`.  A stream that cannot seek raises Y4MError."""
+    if not hasattr(path, "read"):
+        with open(path, "rb") as stream:
+            return index_clip(stream, matrix, range)
+    stream = path
+    seekable = getattr(stream, "seekable", None)
+    if seekable is None or not seekable():
+        raise Y4MError("index_clip needs a stream that can seek (a file, not a pipe)")
+    fmt = read_header(stream, matrix, range)
+    at = stream.tell()
+    end = stream.seek(0, 2)
+    n = fmt.frame_bytes
+    offsets = []
+    while at < end:
+        stream.seek(at)
+        line = _read_line(stream, "FRAME line")
+        if not line.endswith(b"\n"):
+            if b"FRAME".startswith(line[:5]) or line.startswith(b"FRAME"):
+                fmt.truncated = True
+                break
+            raise Y4MError(f"expected FRAME, got {line[:16]!r}")
+        if not line.startswith(b"FRAME") or line[5:6] not in (b" ", b"\n"):
+            raise Y4MError(f"expected FRAME, got {line[:16]!r}")
+        data = at + len(line)
+        if data + n > end:
+            fmt.truncated = True
+            break
+        offsets.append(data)
+        at = data + n
+    return fmt, offsets
+
+
 def write_frame(stream, frame_line, buf):
     stream.write(frame_line)
     stream.write(memoryview(buf).cast("B"))

@@ -1350,22 +1350,22 @@ def median_filter(x, size):
     return out
 
 
-def _triplet_out(t, name, b, h, w, device):
+def _triplet_out(t, name, b, h, w, device, who="triplet_batch_prepare"):
     """(address, slot stride, sample stride) of an output of triplet_batch_prepare: (3, B, 3, h, w), or (3, 3B, h, w) for the
     same layout with dense samples; the (3, h, w) block of a sample is dense, the two outer strides are free."""
     if t is None:
         return None, 0, 0
     if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float32 or t.device != device:
-        raise VfiLibraryError(f"triplet_batch_prepare: {name} must be a float32 tensor on {device}")
+        raise VfiLibraryError(f"{who}: {name} must be a float32 tensor on {device}")
     _lib.check_device(t, name)
     if t.dim() == 4 and tuple(t.shape) == (3, 3 * b, h, w):
         t = t.unflatten(1, (b, 3))
     if t.dim() != 5 or tuple(t.shape) != (3, b, 3, h, w):
-        raise VfiLibraryError(f"triplet_batch_prepare: {name} must be (3, {b}, 3, {h}, {w}) or (3, {3 * b}, {h}, {w}), "
+        raise VfiLibraryError(f"{who}: {name} must be (3, {b}, 3, {h}, {w}) or (3, {3 * b}, {h}, {w}), "
                               f"got {tuple(t.shape)}")
     s0, s1, sc, sh, sw = t.stride()
     if not ((sw == 1 or w == 1) and (sh == w or h == 1) and sc == h * w):
-        raise VfiLibraryError(f"triplet_batch_prepare: {name}: a sample's (3,h,w) block must be dense, strides {t.stride()}")
+        raise VfiLibraryError(f"{who}: {name}: a sample's (3,h,w) block must be dense, strides {t.stride()}")
     return t.data_ptr(), s0, (s1 if b > 1 else 3 * h * w)
 
 
@@ -1402,6 +1402,48 @@ def triplet_batch_prepare(src, params, size, rgb=True, lab=True):
     moved = 3 * b * h * w * (3 + 12 * (rgb is not None) + 12 * (lab is not None))
     _lib.call("vfi_triplet_batch_prepare", _lib.dptr(src, "src", torch.uint8), params.data_ptr(), rp, rs, rb, lp, ls, lb,
               b, hs, ws, h, w, _lib.stream_ptr(), work=("byte", float(moved), "triplet_batch_prepare"))
+    return rgb, lab
+
+
+def yuv_triplet_batch_prepare(src, fmt, params, size, source_size, rgb=True, lab=True):
+    """One training batch from the Y'CbCr frames of a clip (vfi_yuv_triplet_batch_prepare): what triplet_batch_prepare makes
+    of `yuv_to_rgb` of each whole frame, in one launch that decodes only the crops.
+    src: uint8 (B, 3, frame_stride) on the device: the three frames of each sample in the Y4M frame layout, frame_stride >=
+    the frame's bytes, any alignment.  fmt: see _yuv_format.  source_size = (Hs, Ws) of the frames.  params, size, rgb, lab
+    and the result: as triplet_batch_prepare."""
+    who = "yuv_triplet_batch_prepare"
+    if not isinstance(src, torch.Tensor) or not src.is_cuda:
+        raise VfiLibraryError(f"{who}: src must be a tensor on a HIP device (vfi_amd has no CPU path)")
+    cfmt, sub = _yuv_format(fmt, who)
+    hs, ws = int(source_size[0]), int(source_size[1])
+    h, w = int(size[0]), int(size[1])
+    if h <= 0 or w <= 0 or hs <= 0 or ws <= 0:
+        raise VfiLibraryError(f"{who}: bad sizes: crop {h}x{w} of {hs}x{ws}")
+    if src.dtype != torch.uint8 or src.dim() != 3 or src.shape[1] != 3:
+        raise VfiLibraryError(f"{who}: src must be uint8 (B, 3, frame_stride), got {src.dtype} {tuple(src.shape)}")
+    b, _, n = src.shape
+    fs = src.stride(1)
+    if n < yuv_frame_bytes(hs, ws, sub) or (src.stride(2) != 1 and n > 1) or fs < n or (b > 1 and src.stride(0) != 3 * fs):
+        raise VfiLibraryError(f"{who}: src must hold frames of at least {yuv_frame_bytes(hs, ws, sub)} bytes for {hs}x{ws} at one "
+                              f"stride, got shape {tuple(src.shape)} strides {src.stride()}")
+    params = torch.as_tensor(params)
+    if params.is_cuda or params.dtype != torch.int32 or tuple(params.shape) != (b, 3):
+        raise VfiLibraryError(f"{who}: params must be a host int32 tensor of shape ({b}, 3)")
+    params = params.contiguous()
+    if rgb is True:
+        rgb = torch.empty((3, b, 3, h, w), dtype=torch.float32, device=src.device)
+    elif rgb is False:
+        rgb = None
+    if lab is True:
+        lab = torch.empty((3, 3 * b, h, w), dtype=torch.float32, device=src.device)
+    elif lab is False:
+        lab = None
+    rp, rs, rb = _triplet_out(rgb, "rgb", b, h, w, src.device, who)
+    lp, ls, lb = _triplet_out(lab, "lab", b, h, w, src.device, who)
+    _lib.check_device(src, "src")
+    moved = 3 * b * h * w * ((1.5 if sub == YUV_420 else 3) + 12 * (rgb is not None) + 12 * (lab is not None))
+    _lib.call("vfi_yuv_triplet_batch_prepare", src.data_ptr(), fs, ctypes.addressof(cfmt), params.data_ptr(), rp, rs, rb,
+              lp, ls, lb, b, hs, ws, h, w, _lib.stream_ptr(), work=("byte", float(moved), who))
     return rgb, lab
 
 

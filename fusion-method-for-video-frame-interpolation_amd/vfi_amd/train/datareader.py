@@ -37,6 +37,29 @@ def cointoss(p):
     return random.random() < p
 
 
+def draw_params(random_crop, augment_s, augment_t, height, width):
+    """One sample's (crop row i, crop column j, flags) for frames of height x width, drawn as the reference's `__getitem__`
+    draws them: the one parameter draw of every reader here (DBreader_Vimeo90k, clipreader.DBreader_Y4M)."""
+    i = j = 0
+    if random_crop is not None:
+        th, tw = random_crop
+        if height < th or width < tw:
+            raise ValueError(f"Required crop size {(th, tw)} is larger than input image size {(height, width)}")
+        if not (width == tw and height == th):
+            i = torch.randint(0, height - th + 1, size=(1,)).item()
+            j = torch.randint(0, width - tw + 1, size=(1,)).item()
+    flags = 0
+    if augment_s:
+        if cointoss(0.5):
+            flags |= HFLIP
+        if cointoss(0.5):
+            flags |= VFLIP
+    if augment_t:
+        if cointoss(0.5):
+            flags |= SWAP
+    return i, j, flags
+
+
 class DBreader_Vimeo90k(Dataset):
     def __init__(self, db_dir, random_crop=None, resize=None, augment_s=True, augment_t=True):
         db_dir = db_dir + "/sequences"
@@ -83,24 +106,7 @@ class DBreader_Vimeo90k(Dataset):
 
     def draw(self, height, width):
         """One sample's (crop row i, crop column j, flags) for frames of height x width; flags = HFLIP | VFLIP | SWAP."""
-        i = j = 0
-        if self.random_crop is not None:
-            th, tw = self.random_crop
-            if height < th or width < tw:
-                raise ValueError(f"Required crop size {(th, tw)} is larger than input image size {(height, width)}")
-            if not (width == tw and height == th):
-                i = torch.randint(0, height - th + 1, size=(1,)).item()
-                j = torch.randint(0, width - tw + 1, size=(1,)).item()
-        flags = 0
-        if self.augment_s:
-            if cointoss(0.5):
-                flags |= HFLIP
-            if cointoss(0.5):
-                flags |= VFLIP
-        if self.augment_t:
-            if cointoss(0.5):
-                flags |= SWAP
-        return i, j, flags
+        return draw_params(self.random_crop, self.augment_s, self.augment_t, height, width)
 
     def __getitem__(self, index):
         frames = self.images(index)
@@ -140,22 +146,15 @@ class TripletBatch:
     rgb_target = property(lambda self: self.rgb[2])
 
 
-class TripletLoader:
-    """Batches of a DBreader_Vimeo90k on the device.  len = ceil(N / batch_size); the last batch is short, as a DataLoader
-    without drop_last.
-
-    Per batch, the consuming thread draws every sample's parameters in sample order (`dataset.draw`), so results never
-    depend on thread timing or on `workers`.  Decoding runs ahead -- this batch and the next -- on a ThreadPoolExecutor (PIL
-    releases the GIL; no worker processes: the parent has the GPU open, and a fork of it is not a clean process).  The
-    frames are gathered in one of two pinned uint8 staging buffers, copied non-blocking on the current stream, and
-    `ops.triplet_batch_prepare` does the rest in one launch.  A staging buffer is written again only after the event
-    recorded behind its copy.  All samples of a batch must decode to one size.
-
-    shuffle: a `torch.randperm` from `generator` (None: the global generator) at the start of every pass."""
+class StagedLoader:
+    """What the loaders of this package share: the batching of a dataset with `__len__` and `raw(index)`, `raw` running
+    ahead -- this batch and the next -- on a ThreadPoolExecutor, two pinned uint8 staging buffers, each written again only
+    after the event recorded behind its copy, and the non-blocking upload.  A subclass gives `_assemble(indices, futures)`,
+    which turns the `raw` results of one batch into what the loader yields."""
 
     def __init__(self, dataset, batch_size, shuffle=True, workers=4, device="cuda", generator=None, rgb=True, lab=True):
         if batch_size < 1:
-            raise ValueError("TripletLoader: batch_size must be at least 1")
+            raise ValueError(f"{type(self).__name__}: batch_size must be at least 1")
         self.dataset, self.batch_size, self.shuffle = dataset, int(batch_size), shuffle
         self.workers = max(1, min(int(workers), MAX_WORKERS))
         self.device = torch.device(device)
@@ -180,6 +179,46 @@ class TripletLoader:
             self._staging[k] = torch.empty(need, dtype=torch.uint8, pin_memory=self.device.type == "cuda")
         return k, self._staging[k][:need].view(shape)
 
+    def _upload(self, k, stage):
+        """Staging buffer k -> the device, non-blocking on the current stream, with the event that frees the buffer."""
+        src = stage.to(self.device, non_blocking=True)
+        if self.device.type == "cuda":
+            self._events[k] = torch.cuda.Event()
+            self._events[k].record()
+        return src
+
+    def __iter__(self):
+        n = len(self.dataset)
+        order = torch.randperm(n, generator=self.generator).tolist() if self.shuffle else list(range(n))
+        batches = [order[a:a + self.batch_size] for a in range(0, n, self.batch_size)]
+        with ThreadPoolExecutor(max_workers=self.workers) as pool:
+            submit = lambda idx: [pool.submit(self.dataset.raw, i) for i in idx]
+            pending = [submit(b) for b in batches[:2]]
+            try:
+                for t, idx in enumerate(batches):
+                    futures = pending.pop(0)
+                    if t + 2 < len(batches):
+                        pending.append(submit(batches[t + 2]))
+                    yield self._assemble(idx, futures)
+            finally:
+                for futs in pending:
+                    for f in futs:
+                        f.cancel()
+
+
+class TripletLoader(StagedLoader):
+    """Batches of a DBreader_Vimeo90k on the device.  len = ceil(N / batch_size); the last batch is short, as a DataLoader
+    without drop_last.
+
+    Per batch, the consuming thread draws every sample's parameters in sample order (`dataset.draw`), so results never
+    depend on thread timing or on `workers`.  Decoding runs ahead -- this batch and the next -- on a ThreadPoolExecutor (PIL
+    releases the GIL; no worker processes: the parent has the GPU open, and a fork of it is not a clean process).  The
+    frames are gathered in one of two pinned uint8 staging buffers, copied non-blocking on the current stream, and
+    `ops.triplet_batch_prepare` does the rest in one launch.  A staging buffer is written again only after the event
+    recorded behind its copy.  All samples of a batch must decode to one size.
+
+    shuffle: a `torch.randperm` from `generator` (None: the global generator) at the start of every pass."""
+
     def _assemble(self, indices, futures):
         ds = self.dataset
         paths = [str(ds.triplet_list[i]) for i in indices]
@@ -199,27 +238,6 @@ class TripletLoader:
             params[n, 0], params[n, 1], params[n, 2] = ds.draw(shape[0], shape[1])
             for f in range(3):
                 host[n, f] = frames[f]
-        src = stage.to(self.device, non_blocking=True)
-        if self.device.type == "cuda":
-            self._events[k] = torch.cuda.Event()
-            self._events[k].record()
+        src = self._upload(k, stage)
         rgb, lab = ops.triplet_batch_prepare(src, params, ds.crop_size(shape[0], shape[1]), rgb=self.want_rgb, lab=self.want_lab)
         return TripletBatch(lab, rgb, params, paths)
-
-    def __iter__(self):
-        n = len(self.dataset)
-        order = torch.randperm(n, generator=self.generator).tolist() if self.shuffle else list(range(n))
-        batches = [order[a:a + self.batch_size] for a in range(0, n, self.batch_size)]
-        with ThreadPoolExecutor(max_workers=self.workers) as pool:
-            submit = lambda idx: [pool.submit(self.dataset.raw, i) for i in idx]
-            pending = [submit(b) for b in batches[:2]]
-            try:
-                for t, idx in enumerate(batches):
-                    futures = pending.pop(0)
-                    if t + 2 < len(batches):
-                        pending.append(submit(batches[t + 2]))
-                    yield self._assemble(idx, futures)
-            finally:
-                for futs in pending:
-                    for f in futs:
-                        f.cancel()

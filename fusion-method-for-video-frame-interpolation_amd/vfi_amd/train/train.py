@@ -5,7 +5,8 @@ The reference's flags and defaults, plus `--out_dir` (default: the reference's `
 (256 256), `--height` (12, the pyramid's), `--workers` (decoding threads of TripletLoader), `--fixed_stats` (fine-tune on the
 checkpoint's BatchNorm statistics instead of training on the batch's), `--adacof_checkpoint`, `--adacof_config` (accepted for
 the reference's sake; the fusion variant of AdaCoFNet takes no config file) and `--test_paths A B C` (frame 1, target,
-frame 2 of the picture `Trainer.test` writes every 100 batches).  No plots; see trainer.py for the other differences."""
+frame 2 of the picture `Trainer.test` writes every 100 batches).  `--train_clips DIR` (with `--clip_stride`, `--matrix`,
+`--range`) trains from the `*.y4m` clips of DIR instead of `--train` (clipreader.py).  No plots; see trainer.py for the other differences."""
 import argparse
 import datetime
 import os
@@ -15,7 +16,7 @@ import numpy as np
 import torch
 
 from ..phase_net.architecture import PhaseNet
-from .datareader import DBreader_Vimeo90k, TripletLoader
+from . import clipreader
 from .pyramid import Pyramid
 from .trainer import ADACOF_CHECKPOINT, Trainer
 
@@ -28,6 +29,7 @@ parser.add_argument('--gpu_id', type=int, default=0)
 parser.add_argument('--train', type=str, default='./Trainset/vimeo/vimeo_triplet')
 parser.add_argument('--load', type=str, default=None)
 parser.add_argument('--out_dir', type=str, default=None)
+clipreader.add_arguments(parser)       # --train_clips PATH [--clip_stride N --matrix M --range R]: train from .y4m clips
 
 # Learning Options
 parser.add_argument('--epochs', type=int, default=1, help='max epochs')
@@ -86,8 +88,7 @@ def main(argv=None):
 
     device = torch.device(f'cuda:{args.gpu_id}')
     needs_rgb = args.mode == 'fusion' or args.high_level
-    dataset = DBreader_Vimeo90k(args.train, random_crop=tuple(args.crop))
-    train_loader = TripletLoader(dataset, args.batch_size, shuffle=True, workers=args.workers, device=device, rgb=needs_rgb)
+    dataset, train_loader = clipreader.training_input(args, tuple(args.crop), device, rgb=needs_rgb)
 
     pyr = Pyramid(height=args.height, nbands=4, scale_factor=np.sqrt(2), device=device)
     if args.mode == 'fusion':

@@ -892,6 +892,24 @@ int vfi_triplet_batch_prepare(const unsigned char *src, const int *params, float
                               long long rgb_batch_stride, float *lab, long long lab_slot_stride, long long lab_batch_stride,
                               int B, int Hs, int Ws, int h, int w, vfi_stream_t stream);
 
+/* The same batch from the frames of a clip as they lie in a YUV4MPEG2 file: the crop, flips and slot
+ * choice above applied to what vfi_yuv_to_rgb gives for each whole frame, in one pass that decodes only the blocks of the
+ * frame a crop touches.
+ *   src     DEVICE uint8: frame f (0, 1, 2) of sample b starts at src + (3 b + f) * frame_stride, in the frame layout of
+ *           "Clip I/O" below (luma, Cb, Cr; 4:2:0 or 4:4:4); frame_stride >= the frame's bytes, any alignment
+ *   format  HOST int[4] of vfi_yuv_to_rgb (subsampling, siting, matrix, range)
+ *   params, rgb, lab and their strides: as vfi_triplet_batch_prepare; i and j may be odd in 4:2:0
+ * Chroma is up-sampled with indices clamped at the frame's edges, never at the crop's; range, matrix and the clamp to
+ * [0, 1] are vfi_yuv_to_rgb's, and a pixel gets that call's bits (same block ownership, same per-pixel code); Lab is computed
+ * from the clamped rgb in registers.  One launch per 64 samples, no workspace, no atomics, one writer per float.
+ * Checked before anything is enqueued, nothing written: VFI_ERR_INVALID_ARG for a null src, format or params, both outputs
+ * NULL, a size <= 0, an unknown format field, a crop that leaves the source, flags outside 0..7, a stride below 3 * h * w,
+ * frame_stride below the frame's bytes; VFI_ERR_SHAPE for odd Hs or Ws in 4:2:0; VFI_ERR_UNSUPPORTED for Hs * Ws > 2^28. */
+int vfi_yuv_triplet_batch_prepare(const unsigned char *src, long long frame_stride, const int *format, const int *params,
+                                  float *rgb, long long rgb_slot_stride, long long rgb_batch_stride, float *lab,
+                                  long long lab_slot_stride, long long lab_batch_stride, int B, int Hs, int Ws, int h, int w,
+                                  vfi_stream_t stream);
+
 /* ------------------------------------------------------------------------------------
  * LPIPS (piq.LPIPS, reference src/evaluation/evaluate_image.py:22): the head on one tap of the VGG16 trunk, its adjoint,
  * and the input normalisation.  DESIGN.md section 24.  Same rules as the training paths above: no float atomics, one
