@@ -187,23 +187,54 @@ __global__ __launch_bounds__(kTailThreads) void phasenet_level_tail_kernel(const
 static_assert(kTailCh == 4 && kTailStages * kTailCh == 64, "the 8 prediction maps travel as two stages of four planes");
 static_assert(tl::TX % 4 == 0 && kTailThreads % 64 == 0 && kTailThreads <= 1024 && kTailPx <= 32, "every window pixel has a thread; `own` is one word");
 
+// Argument checks shared by the entry point and its query.
+int tail_check_args(const char *who, const float *feat, const float *packed_w, const float *amp_in, const float *max_amp, const float *x_next,
+                    const float *phase_out, const float *amp_out, int N, int H, int W, int Hout, int Wout) {
+    VFI_REQUIRE(feat && packed_w && amp_in && max_amp && x_next && phase_out && amp_out, VFI_ERR_INVALID_ARG, "%s: null pointer", who);
+    VFI_REQUIRE(N > 0 && N <= 65535 && H > 0 && W > 0 && Hout > 0 && Wout > 0, VFI_ERR_INVALID_ARG, "%s: bad sizes", who);
+    const long long HW = (long long)H * W, HWo = (long long)Hout * Wout;
+    VFI_REQUIRE(64 * HW < (1ll << 31), VFI_ERR_UNSUPPORTED, "%s: per-sample tensor too large for 32-bit offsets", who);
+    VFI_REQUIRE(8 * HW <= 64 * HWo, VFI_ERR_UNSUPPORTED, "%s: target %dx%d too small for source %dx%d", who, Hout, Wout, H, W);
+    return VFI_OK;
+}
+
+// Which launches a call takes (VFI_TAIL_PATH_*): the one place the rule lives.  The one-pass kernel runs exactly where
+// vfi_phasenet_predict streams (its fmaf chain; smaller or odd-sized levels run the matrix-core 1x1 there, other bits), so that
+// results never depend on which entry point the caller chose, and only when the target is no smaller than the source along
+// either axis (the window of a tile then fits the LDS planes).  Its stores are 16-byte vectors where every target row is
+// 16-byte aligned.
+int tail_path(const float *feat, long long feat_bstride, const float *amp_in, long long amp_bstride, const float *x_next,
+              long long next_bstride, const float *phase_out, const float *amp_out, int H, int W, int Hout, int Wout) {
+    static const bool stream1x1 = !(getenv("VFI_CONV_STREAM1X1") && atoi(getenv("VFI_CONV_STREAM1X1")) == 0);
+    const long long HW = (long long)H * W;
+    const uintptr_t bits = reinterpret_cast<uintptr_t>(feat) | reinterpret_cast<uintptr_t>(amp_in) | reinterpret_cast<uintptr_t>(phase_out) |
+                           reinterpret_cast<uintptr_t>(amp_out) | (uintptr_t)(feat_bstride * 4) | (uintptr_t)(amp_bstride * 4) | (uintptr_t)(HW * 4);
+    if (!(stream1x1 && HW >= 4096 && (bits & 7u) == 0 && H <= Hout && W <= Wout)) return VFI_TAIL_PATH_TWO_LAUNCHES;
+    const bool vec = Wout % 4 == 0 && (reinterpret_cast<uintptr_t>(x_next) & 15u) == 0 && next_bstride % 4 == 0;
+    return vec ? VFI_TAIL_PATH_ONE_PASS_VEC : VFI_TAIL_PATH_ONE_PASS;
+}
+
 }  // namespace
+
+extern "C" int vfi_phasenet_level_tail_path(const float *feat, long long feat_bstride, const float *packed_w, const float *bias,
+                                            const float *amp_in, long long amp_bstride, const float *max_amp, const float *x_next,
+                                            long long next_bstride, const float *phase_out, const float *amp_out, int N, int H, int W,
+                                            int Hout, int Wout) {
+    (void)bias;
+    if (const int rc = tail_check_args("vfi_phasenet_level_tail_path", feat, packed_w, amp_in, max_amp, x_next, phase_out, amp_out, N, H, W, Hout, Wout))
+        return rc;
+    return tail_path(feat, feat_bstride, amp_in, amp_bstride, x_next, next_bstride, phase_out, amp_out, H, W, Hout, Wout);
+}
 
 extern "C" int vfi_phasenet_level_tail(const float *feat, long long feat_bstride, const float *packed_w, const float *bias,
                                        const float *amp_in, long long amp_bstride, const float *max_amp, float *x_next,
                                        long long next_bstride, float *phase_out, float *amp_out, int N, int H, int W, int Hout, int Wout,
                                        vfi_stream_t stream) {
-    VFI_REQUIRE(feat && packed_w && amp_in && max_amp && x_next && phase_out && amp_out, VFI_ERR_INVALID_ARG, "vfi_phasenet_level_tail: null pointer");
-    VFI_REQUIRE(N > 0 && N <= 65535 && H > 0 && W > 0 && Hout > 0 && Wout > 0, VFI_ERR_INVALID_ARG, "vfi_phasenet_level_tail: bad sizes");
-    const long long HW = (long long)H * W, HWo = (long long)Hout * Wout;
-    VFI_REQUIRE(64 * HW < (1ll << 31), VFI_ERR_UNSUPPORTED, "vfi_phasenet_level_tail: per-sample tensor too large for 32-bit offsets");
-    VFI_REQUIRE(8 * HW <= 64 * HWo, VFI_ERR_UNSUPPORTED, "vfi_phasenet_level_tail: target %dx%d too small for source %dx%d", Hout, Wout, H, W);
-    // The one-pass kernel runs exactly where vfi_phasenet_predict streams (its fmaf chain; smaller or odd-sized levels run the
-    // matrix-core 1x1 there, other bits): results never depend on which entry point the caller chose.
-    static const bool stream1x1 = !(getenv("VFI_CONV_STREAM1X1") && atoi(getenv("VFI_CONV_STREAM1X1")) == 0);
-    const uintptr_t bits = reinterpret_cast<uintptr_t>(feat) | reinterpret_cast<uintptr_t>(amp_in) | reinterpret_cast<uintptr_t>(phase_out) |
-                           reinterpret_cast<uintptr_t>(amp_out) | (uintptr_t)(feat_bstride * 4) | (uintptr_t)(amp_bstride * 4) | (uintptr_t)(HW * 4);
-    if (!(stream1x1 && HW >= 4096 && (bits & 7u) == 0 && H <= Hout && W <= Wout)) {
+    if (const int rc = tail_check_args("vfi_phasenet_level_tail", feat, packed_w, amp_in, max_amp, x_next, phase_out, amp_out, N, H, W, Hout, Wout))
+        return rc;
+    const long long HWo = (long long)Hout * Wout;
+    const int path = tail_path(feat, feat_bstride, amp_in, amp_bstride, x_next, next_bstride, phase_out, amp_out, H, W, Hout, Wout);
+    if (path == VFI_TAIL_PATH_TWO_LAUNCHES) {
         // the launches this entry point replaces; the un-resized prediction planes pass through the head of the target's
         // feature planes, which the last launch overwrites
         int rc = vfi_phasenet_predict(feat, feat_bstride, packed_w, bias, amp_in, amp_bstride, max_amp, x_next, next_bstride, phase_out, amp_out, N,
@@ -211,7 +242,7 @@ extern "C" int vfi_phasenet_level_tail(const float *feat, long long feat_bstride
         if (!rc) rc = vfi_resize_bilinear(x_next, next_bstride, nullptr, 0, x_next + 64 * HWo, next_bstride, N, 8, H, W, Hout, Wout, 0, 0, stream);
         return rc ? rc : vfi_resize_bilinear(feat, feat_bstride, nullptr, 0, x_next, next_bstride, N, 64, H, W, Hout, Wout, 0, 0, stream);
     }
-    const bool vec = Wout % 4 == 0 && (reinterpret_cast<uintptr_t>(x_next) & 15u) == 0 && next_bstride % 4 == 0;
+    const bool vec = path == VFI_TAIL_PATH_ONE_PASS_VEC;
     const dim3 grid(vfi::ceil_div(Wout, tl::TX), vfi::ceil_div(Hout, tl::TY), N);
     VFI_REQUIRE(grid.y <= 65535, VFI_ERR_UNSUPPORTED, "vfi_phasenet_level_tail: target of %d rows", Hout);
     hipStream_t s = vfi::as_stream(stream);

@@ -43,6 +43,7 @@ SIGNATURES = {
     "vfi_phasenet_emit": [c_f, c_l, c_f, c_l, c_f, c_f, c_f, c_i, c_i, c_s],
     "vfi_phasenet_predict": [c_f, c_l, c_f, c_f, c_f, c_l, c_f, c_f, c_l, c_f, c_f, c_i, c_i, c_i, c_i, c_s],
     "vfi_phasenet_level_tail": [c_f, c_l, c_f, c_f, c_f, c_l, c_f, c_f, c_l, c_f, c_f, c_i, c_i, c_i, c_i, c_i, c_s],
+    "vfi_phasenet_level_tail_path": [c_f, c_l, c_f, c_f, c_f, c_l, c_f, c_f, c_l, c_f, c_f, c_i, c_i, c_i, c_i, c_i],
     "vfi_phasenet_emit_low": [c_f, c_l, c_f, c_l, c_f, c_f, c_i, c_i, c_s],
     "vfi_phasenet_emit_n": [c_f, c_l, c_f, c_l, c_f, c_f, c_f, c_i, c_i, c_i, c_s],
     "vfi_phasenet_predict_n": [c_f, c_l, c_f, c_f, c_f, c_l, c_f, c_f, c_l, c_f, c_f, c_i, c_i, c_i, c_i, c_i, c_s],

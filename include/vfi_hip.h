@@ -291,6 +291,17 @@ int vfi_phasenet_level_tail(const float *feat, long long feat_bstride, const flo
                             const float *amp_in, long long amp_bstride, const float *max_amp, float *x_next,
                             long long next_bstride, float *phase_out, float *amp_out, int N, int H, int W, int Hout, int Wout,
                             vfi_stream_t stream);
+/* Which launches vfi_phasenet_level_tail takes for these arguments (no GPU call; >= 0: VFI_TAIL_PATH_*, < 0: the status the
+ * entry point would return for them): vfi_phasenet_predict and vfi_resize_bilinear, the one-pass kernel with element / 4-byte
+ * aligned stores, or the one-pass kernel with 16-byte aligned vector stores (Wout a multiple of 4, x_next and its batch stride
+ * 16-byte aligned).  The one-pass kernel runs for an even number of >= 4096 source pixels, 8-byte-aligned feat, amp_in,
+ * phase_out, amp_out and batch strides, H <= Hout and W <= Wout.  For tests: the rule lives in the library only, as with
+ * vfi_conv2d_algo. */
+enum { VFI_TAIL_PATH_TWO_LAUNCHES = 0, VFI_TAIL_PATH_ONE_PASS = 1, VFI_TAIL_PATH_ONE_PASS_VEC = 2 };
+int vfi_phasenet_level_tail_path(const float *feat, long long feat_bstride, const float *packed_w, const float *bias,
+                                 const float *amp_in, long long amp_bstride, const float *max_amp, const float *x_next,
+                                 long long next_bstride, const float *phase_out, const float *amp_out, int N, int H, int W,
+                                 int Hout, int Wout);
 
 /* phase_net.py:113-116 + :96-98: low_out (N,HW) = (a*low_in[:,0] + (1-a)*low_in[:,1])*max_low[n], a = (pred+1)/2. */
 int vfi_phasenet_emit_low(const float *pred, long long pred_bstride, const float *low_in, long long low_bstride,

@@ -5,7 +5,9 @@
 //   * the window fits the kernel's LDS planes (MAX_ROWS x MAX_COLS);
 //   * both bilinear taps of every target pixel of a tile lie inside its window.
 // Run over the 15 consecutive level pairs of a 1080p and of a 720p pyramid (sqrt(2) steps) and 400 random pairs with
-// 1 <= H / h <= 2.  Built and run by tests/test_phasenet_tail_host.py (hipcc --cuda-host-only).
+// 1 <= H / h <= 2; then over what the entry point accepts beyond that: 20 pairs with an exact scale of 1 along one axis or
+// both, exact x2, x3 and x8 and the shapes tests/test_phasenet_head_f64_gpu.py launches, and 1500 random pairs with
+// 1 <= H / h <= 8 and 1 <= W / w <= 8 drawn independently.  Built and run by tests/test_phasenet_tail_host.py (hipcc --cuda-host-only).
 #include <cmath>
 #include <cstdio>
 #include <vector>
@@ -74,6 +76,22 @@ int main() {
     for (int i = 0; i < 400; ++i, ++pairs) {
         const int h = 1 + rnd(i % 4 == 0 ? 900 : 200), w = 1 + rnd(i % 4 == 0 ? 1400 : 300);
         bad += check_pair(h, w, h + rnd(h + 1), w + rnd(w + 1), count);
+    }
+    // What the entry point accepts beyond that (h <= H, w <= W, any ratio): an exact scale along one axis or both, exact
+    // multiples, and 1500 random pairs of ratio 1..8 per axis.
+    const int exact[][4] = {{64, 64, 64, 64},     {1, 1, 1, 1},        {17, 300, 17, 300},  {48, 86, 48, 258},   {200, 130, 283, 130},
+                            {37, 129, 37, 183},   {64, 66, 128, 132},  {1, 1, 2, 2},        {135, 240, 270, 480}, {33, 47, 99, 141},
+                            {1, 129, 3, 387},     {32, 128, 256, 1024}, {1, 1, 8, 8},       {17, 131, 136, 1048}, {4, 1024, 5, 1449},
+                            {1024, 4, 1449, 6},   {46, 90, 65, 127},   {50, 82, 71, 129},   {135, 240, 191, 340},
+                            {62, 68, 64, 70}};
+    for (const auto &e : exact) {
+        bad += check_pair(e[0], e[1], e[2], e[3], count);
+        ++pairs;
+    }
+    for (int i = 0; i < 1500; ++i, ++pairs) {
+        const int h = 1 + rnd(i % 8 == 0 ? 300 : 60), w = 1 + rnd(i % 8 == 0 ? 500 : 150);
+        const int H = h + rnd(7 * h + 1), W = w + rnd(7 * w + 1);         // h <= H <= 8 h
+        bad += check_pair(h, w, H, W, count);
     }
     std::printf("checked %ld level pairs, %ld violations\n", pairs, bad);
     return bad ? 1 : 0;
